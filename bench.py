@@ -23,15 +23,30 @@ is resident in HBM before it starts.  Launch:
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line.  Extra objects in that line:
+A plain run sets up, warms up, times ONE loop of exactly K steps, writes the
+outputs of the last step if `--dump-outputs DIR` is given, and prints ONE JSON
+line (rank 0) with the headline: metric, value, unit, ms_per_step, ...
+
+`--full` adds everything else to that line:
   roofline      achieved algorithmic HBM GB/s of the scan kernels (HIP events on
                 the library's own stream) against the 8 TB/s HBM3E peak and
                 against the read bandwidth measured on this device
   cpu_baseline  the oracle (plain-C restatement of the reference) on ONE host
                 core on a bounded sample of the same batch, and on one worker
                 process per core (`np`, the reference's deployment model)
-  device_resident_qps / blocking_qps / latency / tfidf / default_limit / fuzzy
+  device_resident_qps / blocking_qps / latency / tfidf / default_limit / fuzzy / refresh
                 side measurements (N = 1 only)
+and repeats the loop of K steps until --min-seconds (default 1 s) have been
+timed, reporting the median loop.
+
+`--dump-outputs DIR`: the batch of the last timed step is searched once more
+after the timed loop, through the same API with the same parameters (the search
+is deterministic), and what a caller receives is written as DIR/<name>.npy:
+doc_ids (float64, -1 past a query's count; ids >= 2^53 as doc_ids_hi32 +
+doc_ids_lo32), scores (float32, 0 past the count), counts (float64, -1 for a
+failed query), query_index (float64: the batch rows written -- all of them, or
+a fixed seeded sample when the whole batch would exceed 64 MB).  The inputs are
+seeded: the same arguments give the same arrays from run to run.
 """
 import argparse
 import ctypes as C
@@ -82,11 +97,16 @@ def parse_args():
                     help="batches in flight in the timed loop (default: 3; 4 for limits above 64, whose "
                          "batches end in milliseconds of heap replay)")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--min-seconds", type=float, default=1.0,
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: roofline and per-kernel figures, side measurements, "
+                         "CPU baselines, repeated timed loops (see --min-seconds)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step as DIR/<name>.npy")
+    ap.add_argument("--min-seconds", type=float, default=None,
                     help="repeat the timed loop of --steps steps until this much time has been measured; the line "
-                         "reports the median loop (0: one loop)")
+                         "reports the median loop (0: one loop; default: 1 with --full, else 0)")
     ap.add_argument("--cpu-seconds", type=float, default=20.0,
-                    help="budget of the CPU-baseline sample (0 = skip)")
+                    help="--full: budget of the CPU-baseline sample (0 = skip)")
     ap.add_argument("--np", type=int, default=0,
                     help="worker processes of the CPU-NP baseline (0 = every core of the host share)")
     ap.add_argument("--rotate", type=int, default=4,
@@ -97,11 +117,13 @@ def parse_args():
     ap.add_argument("--sparse-ids", action="store_true",
                     help="corpus with sparse random u64 doc ids (SURVEY 8d: exercises the ordinal map)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the latency / fuzzy / device-resident side measurements")
+                    help="--full: skip the latency / fuzzy / device-resident side measurements")
     ap.add_argument("--workdir", default=None)
     ap.add_argument("--keep", action="store_true")
     ap.add_argument("--cpu-np-worker", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.min_seconds is None:
+        a.min_seconds = 1.0 if a.full else 0.0
     d, t, b, _ = WORKLOADS[a.workload]
     a.docs = a.docs or d
     a.terms = a.terms or t
@@ -139,6 +161,57 @@ def make_queries(args, terms, n, corpus, variant=0):
 
 def c_strings(qs):
     return (C.c_char_p * max(len(qs), 1))(*[q.encode() if isinstance(q, str) else q for q in qs])
+
+
+DUMP_BYTES = 64_000_000         # --dump-outputs: at most this much in all
+
+
+def dump_outputs(args, rank, batch, search):
+    """--dump-outputs: `search(arr, n, resps, errs)` runs the batch of strings `batch` once, as the
+    timed path does; every rank calls it (a sharded batch is collective), rank 0 writes what a caller
+    receives as args.dump_outputs/<name>.npy.  Rows past 64 MB in all: a fixed seeded sample."""
+    import numpy as np
+    import nxsearch_amd as N
+    L = N.lib()
+    n, k = len(batch), max(args.limit, 1)
+    split = args.sparse_ids                     # random u64 ids: beyond float64's 53-bit mantissa
+    row_bytes = k * (4 + (16 if split else 8)) + 16
+    rows = np.arange(n)
+    if n * row_bytes > DUMP_BYTES:
+        keep = max(1, DUMP_BYTES // row_bytes)
+        rows = np.sort(np.random.default_rng(12345).choice(n, size=keep, replace=False))
+    resps = (C.c_void_p * max(n, 1))()
+    errs = (C.c_int * max(n, 1))()
+    search(c_strings(batch), n, resps, errs)
+    ids = np.zeros((len(rows), k), dtype=np.uint64)
+    scores = np.zeros((len(rows), k), dtype=np.float32)
+    counts = np.full(len(rows), -1.0)
+    d, sc = C.c_uint64(), C.c_float()
+    for j, i in enumerate(rows):
+        r = resps[i]
+        if not r:
+            continue
+        L.nxs_resp_iter_reset(r)
+        c = 0
+        while c < k and L.nxs_resp_iter_result(r, C.byref(d), C.byref(sc)):
+            ids[j, c], scores[j, c] = d.value, sc.value
+            c += 1
+        counts[j] = c
+    for i in range(n):
+        if resps[i]:
+            L.nxs_resp_release(resps[i])
+    if rank != 0:
+        return
+    valid = np.arange(k)[None, :] < counts[:, None]
+    out = {"scores": scores, "counts": counts, "query_index": rows.astype(np.float64)}
+    if split or int(ids.max(initial=0)) >= 1 << 53:
+        out["doc_ids_hi32"] = np.where(valid, (ids >> np.uint64(32)).astype(np.float64), -1.0)
+        out["doc_ids_lo32"] = np.where(valid, (ids & np.uint64(0xffffffff)).astype(np.float64), -1.0)
+    else:
+        out["doc_ids"] = np.where(valid, ids.astype(np.float64), -1.0)
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
 
 
 def main():
@@ -271,12 +344,13 @@ def main():
             raise N.NxsError(*nxs.error())
         return out
 
-    # measured HBM read rate of this device (roofline denominator), before the
-    # timed region: it also brings the memory clocks up
+    # measured HBM read rate of this device (roofline denominator, reported with --full), before the
+    # timed region: it also brings the memory clocks up, so every run does it as part of the warm-up
     measured = L.nxsgpu_hbm_read_gbs(idx.device, 5)
     run(args.warmup)
-    idx.set_profiling(True)
-    idx.profile(reset=True)
+    if args.full:
+        idx.set_profiling(True)
+        idx.profile(reset=True)
     idx.host_profile()
 
     own_loops = []
@@ -311,9 +385,22 @@ def main():
         loops.append(dt)
         res.results += r2.results
         res.failed += r2.failed
-    prof = idx.profile(reset=True)
+    prof = idx.profile(reset=True) if args.full else None
     host_prof = idx.host_profile()
     idx.set_profiling(False)
+    if args.dump_outputs and args.steps > 0:
+        # what the last timed step computed: its batch once more, through the same API and parameters
+        if sharded:
+            idx.shard_local(False)      # rank 0 receives every query's results
+        last = batches[(args.steps - 1) % n_sets]
+
+        def last_step(arr, n, resps, errs):
+            if L.nxs_index_search_batch_begin(idx._h, params, arr, n) != 0 or \
+                    L.nxs_index_search_batch_end(idx._h, resps, errs) < 0:
+                raise N.NxsError(*nxs.error())
+        dump_outputs(args, rank, last, last_step)
+        if sharded:
+            idx.shard_local(True)
     elapsed = sorted(loops)[(len(loops) - 1) // 2]          # the median loop (the lower one of an even count)
     # N > 1: evidence that RCCL saw N ranks -- its own count of the communicator, every rank's own loop
     # time (the line's figure is their MAX), what the all-gathers carried
@@ -345,76 +432,77 @@ def main():
     qps = total_q / elapsed
     ms_per_step = 1e3 * elapsed / args.steps
 
-    # ---- roofline of the dominant kernels (the scan launches) on this rank ----
-    launches = max(prof["launches"], 1)
-    my_share = 1.0      # (sharded: a rank walks the responses of its own slice only -- nxs_index_shard_local)
-    matched = res_results_per_loop / max(args.steps, 1) * my_share
-    alg_bytes = prof["postings"] * POSTING_BYTES / launches + matched * RESULT_BYTES
-    # first scan launch -> every class scanned and replayed (classes overlap: the
-    # sparse + dense OR class runs on a stream of its own beside the others)
-    scan_ms = (prof["scan_ms"] + prof["replay_ms"]) / launches
-    achieved = alg_bytes / (scan_ms * 1e-3) / 1e9 if scan_ms > 0 else 0.0
-    traffic, traffic_src, traffic_per_kernel = pmc_traffic(args, world)
-    # One scan launch per query class and step, each timed with HIP events on the stream it is
-    # launched on (nxsgpu_profile_t::cls_*).  Per class: ms = the events' span per launch; alg_bytes =
-    # 8 B x the class's postings (what the reference's loops touch) -- for classes that SKIP
-    # postings (k_scanr / k_scanq: intersect first; k_cold + k_scanm<.., DROP>: dense lists not read) that
-    # is work done, not bytes moved, so it is reported as a rate (work_equiv_gbs), never as a fraction;
-    # moved_bytes = the kernel's FETCH_SIZE x factor + WRITE_SIZE from the committed rocprofv3 --pmc
-    # summary of this command (traffic_source; not collected inside this run), frac_moved = moved / ms / peak.
-    mode = 0 if args.limit <= 64 else 3
-    per_kernel = []
-    for c in prof.get("classes", []):
-        if not c["launches"] or c["ms"] <= 0:
-            continue
-        names = class_kernels(c["key"], mode)
-        ms = c["ms"] / c["launches"]
-        algb = c["postings"] * POSTING_BYTES / c["launches"]
-        moved = sum(traffic_per_kernel.get(n, 0) for n in names) if all(n in traffic_per_kernel for n in names) else None
-        per_kernel.append({"kernel": "+".join(names), "queries": int(c["queries"] / c["launches"]),
-                           "ms": round(ms, 4), "alg_bytes": int(algb),
-                           "work_equiv_gbs": round(algb / (ms * 1e-3) / 1e9, 1),
-                           "moved_bytes": moved,
-                           "moved_gbs": round(moved / (ms * 1e-3) / 1e9, 1) if moved else None,
-                           "frac_moved": round(moved / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if moved else None})
-    per_kernel.sort(key=lambda e: -e["ms"])
-    # the dominant kernel: the class that moves the most bytes (classes overlap on two streams, so a
-    # latency-bound class with few wavefronts can span longer than the one that keeps the chip busy);
-    # without a PMC summary: the longest one
-    with_moved = [e for e in per_kernel if e["moved_bytes"]]
-    # (an entry without bytes of its own -- a class's top ranges sent ahead: counted with the class -- is never the dominant one)
-    with_bytes = [e for e in per_kernel if e["alg_bytes"] > 0]
-    dom = max(with_moved, key=lambda e: e["moved_bytes"]) if with_moved else (with_bytes[0] if with_bytes else (per_kernel[0] if per_kernel else None))
-    # the dominant kernel's own roofline point.  If it streams every posting it is charged for
-    # (k_scanm, k_scan1) algorithmic == moved and the fraction is a bandwidth fraction; a kernel that
-    # skips postings gets its fraction from the bytes it MOVED (never above 1).
-    if dom:
-        dom_alg = dom["work_equiv_gbs"]
-        basis = "algorithmic"
-        dom_ach = dom_alg
-        if dom["moved_gbs"] is not None and (dom_alg > HBM_PEAK_GBS or dom["moved_bytes"] < 0.8 * dom["alg_bytes"]):
-            dom_ach, basis = dom["moved_gbs"], "moved"
-        elif dom_alg > HBM_PEAK_GBS:
-            dom_ach, basis = None, "work-equivalent only (the kernel skips postings; no PMC summary for it)"
-    roofline = {"bound": "hbm", "kernel": dom["kernel"] if dom else None,
-                "achieved": round(dom_ach, 1) if dom and dom_ach is not None else None,
-                "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(dom_ach / HBM_PEAK_GBS, 4) if dom and dom_ach is not None else None,
-                "achieved_basis": basis if dom else None,
-                "kernel_ms": dom["ms"] if dom else None,
-                "peak_measured": round(measured, 1),
-                "frac_measured": round(dom_ach / measured, 4) if dom and dom_ach is not None and measured > 0 else None,
-                "traffic": dom["moved_bytes"] if dom else None, "traffic_source": traffic_src,
-                "per_kernel": per_kernel,
-                # the whole step: all classes, first scan launch -> last replay (classes overlap on two
-                # streams); a rate of work done -- the AND half and the dense-OR class are charged for
-                # postings they never read -- NOT a bandwidth fraction
-                "step": {"alg_bytes_per_launch": int(alg_bytes), "span_ms": round(scan_ms, 4),
-                         "work_equiv_gbs": round(achieved, 1),
-                         "moved_bytes_per_launch": traffic,
-                         "moved_gbs": round(traffic / (scan_ms * 1e-3) / 1e9, 1) if traffic and scan_ms > 0 else None,
-                         "frac_moved": round(traffic / (scan_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if traffic and scan_ms > 0 else None,
-                         "of_which_after_last_scan_ms": round(prof["replay_ms"] / launches, 4)}}
+    roofline, traffic_per_kernel, mode = None, {}, 0 if args.limit <= 64 else 3
+    if args.full:
+        # ---- --full: roofline of the dominant kernels (the scan launches) on this rank ----
+        launches = max(prof["launches"], 1)
+        my_share = 1.0      # (sharded: a rank walks the responses of its own slice only -- nxs_index_shard_local)
+        matched = res_results_per_loop / max(args.steps, 1) * my_share
+        alg_bytes = prof["postings"] * POSTING_BYTES / launches + matched * RESULT_BYTES
+        # first scan launch -> every class scanned and replayed (classes overlap: the
+        # sparse + dense OR class runs on a stream of its own beside the others)
+        scan_ms = (prof["scan_ms"] + prof["replay_ms"]) / launches
+        achieved = alg_bytes / (scan_ms * 1e-3) / 1e9 if scan_ms > 0 else 0.0
+        traffic, traffic_src, traffic_per_kernel = pmc_traffic(args, world)
+        # One scan launch per query class and step, each timed with HIP events on the stream it is
+        # launched on (nxsgpu_profile_t::cls_*).  Per class: ms = the events' span per launch; alg_bytes =
+        # 8 B x the class's postings (what the reference's loops touch) -- for classes that SKIP
+        # postings (k_scanr / k_scanq: intersect first; k_cold + k_scanm<.., DROP>: dense lists not read) that
+        # is work done, not bytes moved, so it is reported as a rate (work_equiv_gbs), never as a fraction;
+        # moved_bytes = the kernel's FETCH_SIZE x factor + WRITE_SIZE from the committed rocprofv3 --pmc
+        # summary of this command (traffic_source; not collected inside this run), frac_moved = moved / ms / peak.
+        per_kernel = []
+        for c in prof.get("classes", []):
+            if not c["launches"] or c["ms"] <= 0:
+                continue
+            names = class_kernels(c["key"], mode)
+            ms = c["ms"] / c["launches"]
+            algb = c["postings"] * POSTING_BYTES / c["launches"]
+            moved = sum(traffic_per_kernel.get(n, 0) for n in names) if all(n in traffic_per_kernel for n in names) else None
+            per_kernel.append({"kernel": "+".join(names), "queries": int(c["queries"] / c["launches"]),
+                               "ms": round(ms, 4), "alg_bytes": int(algb),
+                               "work_equiv_gbs": round(algb / (ms * 1e-3) / 1e9, 1),
+                               "moved_bytes": moved,
+                               "moved_gbs": round(moved / (ms * 1e-3) / 1e9, 1) if moved else None,
+                               "frac_moved": round(moved / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if moved else None})
+        per_kernel.sort(key=lambda e: -e["ms"])
+        # the dominant kernel: the class that moves the most bytes (classes overlap on two streams, so a
+        # latency-bound class with few wavefronts can span longer than the one that keeps the chip busy);
+        # without a PMC summary: the longest one
+        with_moved = [e for e in per_kernel if e["moved_bytes"]]
+        # (an entry without bytes of its own -- a class's top ranges sent ahead: counted with the class -- is never the dominant one)
+        with_bytes = [e for e in per_kernel if e["alg_bytes"] > 0]
+        dom = max(with_moved, key=lambda e: e["moved_bytes"]) if with_moved else (with_bytes[0] if with_bytes else (per_kernel[0] if per_kernel else None))
+        # the dominant kernel's own roofline point.  If it streams every posting it is charged for
+        # (k_scanm, k_scan1) algorithmic == moved and the fraction is a bandwidth fraction; a kernel that
+        # skips postings gets its fraction from the bytes it MOVED (never above 1).
+        if dom:
+            dom_alg = dom["work_equiv_gbs"]
+            basis = "algorithmic"
+            dom_ach = dom_alg
+            if dom["moved_gbs"] is not None and (dom_alg > HBM_PEAK_GBS or dom["moved_bytes"] < 0.8 * dom["alg_bytes"]):
+                dom_ach, basis = dom["moved_gbs"], "moved"
+            elif dom_alg > HBM_PEAK_GBS:
+                dom_ach, basis = None, "work-equivalent only (the kernel skips postings; no PMC summary for it)"
+        roofline = {"bound": "hbm", "kernel": dom["kernel"] if dom else None,
+                    "achieved": round(dom_ach, 1) if dom and dom_ach is not None else None,
+                    "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(dom_ach / HBM_PEAK_GBS, 4) if dom and dom_ach is not None else None,
+                    "achieved_basis": basis if dom else None,
+                    "kernel_ms": dom["ms"] if dom else None,
+                    "peak_measured": round(measured, 1),
+                    "frac_measured": round(dom_ach / measured, 4) if dom and dom_ach is not None and measured > 0 else None,
+                    "traffic": dom["moved_bytes"] if dom else None, "traffic_source": traffic_src,
+                    "per_kernel": per_kernel,
+                    # the whole step: all classes, first scan launch -> last replay (classes overlap on two
+                    # streams); a rate of work done -- the AND half and the dense-OR class are charged for
+                    # postings they never read -- NOT a bandwidth fraction
+                    "step": {"alg_bytes_per_launch": int(alg_bytes), "span_ms": round(scan_ms, 4),
+                             "work_equiv_gbs": round(achieved, 1),
+                             "moved_bytes_per_launch": traffic,
+                             "moved_gbs": round(traffic / (scan_ms * 1e-3) / 1e9, 1) if traffic and scan_ms > 0 else None,
+                             "frac_moved": round(traffic / (scan_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if traffic and scan_ms > 0 else None,
+                             "of_which_after_last_scan_ms": round(prof["replay_ms"] / launches, 4)}}
 
     what = WORKLOADS[args.workload][3] % args.limit
     out = {
@@ -446,7 +534,7 @@ def main():
         "setup_s": {"corpus": round(t_gen, 1), "index_load": round(t_load, 1)},
     }
 
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         # The classes of a step overlap on three streams, so a class's event span above includes the time it
         # shares the chip with the others.  The same rotated loop once more with every class on ONE stream, one
         # after the other (nothing beside the scan stream, nothing sent ahead): each kernel's own duration, and
@@ -546,9 +634,20 @@ def docshard_bench(args, info, terms, corpus, work, t_gen):
     t0 = time.perf_counter()
     run(args.steps)
     elapsed = time.perf_counter() - t0
-    # parity sample against the whole-index oracle
+    if args.dump_outputs and args.steps > 0:
+        # what the last timed step computed: its batch once more, through the same API and parameters
+        def last_step(arr, n, resps, errs):
+            DL = N.lib()
+            DL.nxs_docshard_search_batch.restype = C.c_int
+            DL.nxs_docshard_search_batch.argtypes = [C.POINTER(C.c_void_p), C.c_uint, C.c_void_p,
+                                                     C.POINTER(C.c_char_p), C.c_size_t,
+                                                     C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
+            if DL.nxs_docshard_search_batch(hs, S, params, arr, n, resps, errs) < 0:
+                raise N.NxsError(*nxs.error())
+        dump_outputs(args, 0, batches[(args.steps - 1) % n_sets], last_step)
+    # --full: parity sample against the whole-index oracle
     mism = None
-    if args.cpu_seconds > 0:
+    if args.full and args.cpu_seconds > 0:
         import oracle_lib as O
         oidx = O.Index(info["terms"], info["dtmap"])
         sample = batches[0][:max(4, min(24, int(args.cpu_seconds)))]

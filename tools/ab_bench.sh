@@ -1,7 +1,8 @@
 #!/bin/bash
 # A/B of the C3 bench inside one session: "name:ENV=val,ENV=val" or "name:lib=<variant suffix>" per argument
 # usage: tools/ab_bench.sh [--rounds N] spec...
-mkdir -p gpurun_out/r5/ab
+out=${OUT:-out}/ab
+mkdir -p "$out"
 ROUNDS=2
 if [ "$1" = "--rounds" ]; then ROUNDS=$2; shift 2; fi
 C=$PWD/nxsearch_amd/csrc
@@ -15,9 +16,9 @@ for spec in "$@"; do
         ?*=*) export "$e";;
       esac
     done
-    NXS_BENCH_SERIAL=1 timeout -k 10 200 python bench.py --cpu-seconds 0 --no-extras --steps 100 > gpurun_out/r5/ab/$name.$r.json 2>/dev/null
+    NXS_BENCH_SERIAL=1 timeout -k 10 200 python bench.py --full --cpu-seconds 0 --no-extras --steps 100 > "$out/$name.$r.json" 2>/dev/null
   )
-  python - "$name" gpurun_out/r5/ab/$name.$r.json <<'PY'
+  python - "$name" "$out/$name.$r.json" <<'PY'
 import json, sys
 try:
     d = json.load(open(sys.argv[2]))

@@ -1,7 +1,8 @@
 #!/bin/bash
 # A/B of a bench workload's host pipeline inside one session: "name:ENV=val,ENV=val" per argument
 # usage: tools/ab_c4.sh [--workload C4|C5] [--rounds N] spec...
-mkdir -p gpurun_out/r5/ab
+out=${OUT:-out}/ab
+mkdir -p "$out"
 W=C4; ROUNDS=2
 while [ "${1#--}" != "$1" ]; do
   case "$1" in --workload) W=$2; shift 2;; --rounds) ROUNDS=$2; shift 2;; *) break;; esac
@@ -12,9 +13,9 @@ for spec in "$@"; do
   name=${spec%%:*}; kv=${spec#*:}
   (
     IFS=','; for e in $kv; do case "$e" in ?*=*) export "$e";; esac; done
-    timeout -k 10 400 python bench.py --workload $W --cpu-seconds 0 --no-extras --steps $STEPS > gpurun_out/r5/ab/$W.$name.$r.json 2>gpurun_out/r5/ab/$W.$name.$r.err
+    timeout -k 10 400 python bench.py --full --workload $W --cpu-seconds 0 --no-extras --steps $STEPS > "$out/$W.$name.$r.json" 2>"$out/$W.$name.$r.err"
   )
-  python - "$name" gpurun_out/r5/ab/$W.$name.$r.json <<'PY'
+  python - "$name" "$out/$W.$name.$r.json" <<'PY'
 import json, sys
 try:
     d = json.load(open(sys.argv[2]))

@@ -1,13 +1,14 @@
 #!/bin/bash
 # A/B of the default-limit batch (params == NULL => 1000) inside one session: "name:ENV=val,ENV=val" per argument
-mkdir -p gpurun_out/r5/ab
+out=${OUT:-out}/ab
+mkdir -p "$out"
 for spec in "$@"; do
   name=${spec%%:*}; kv=${spec#*:}
   (
     IFS=','; for e in $kv; do case "$e" in ?*=*) export "$e";; esac; done
-    timeout -k 10 300 python bench.py --limit 1000 --depth 4 --cpu-seconds 0 --no-extras --steps 30 > gpurun_out/r5/ab/L.$name.json 2>gpurun_out/r5/ab/L.$name.err
+    timeout -k 10 300 python bench.py --full --limit 1000 --depth 4 --cpu-seconds 0 --no-extras --steps 30 > "$out/L.$name.json" 2>"$out/L.$name.err"
   )
-  python - "$name" gpurun_out/r5/ab/L.$name.json <<'PY'
+  python - "$name" "$out/L.$name.json" <<'PY'
 import json, sys
 try:
     d = json.load(open(sys.argv[2]))

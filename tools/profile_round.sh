@@ -12,11 +12,11 @@ export TMPDIR=/tmp
 note() { echo "[profile_round $(date +%T)] $*"; }
 
 # (2) C3: kernel stats + counters.  8 steps = every one of the 4 rotated batches twice
-B="python3 bench.py --steps 7 --warmup 1 --cpu-seconds 0 --no-extras --min-seconds 0"
+B="python3 bench.py --full --steps 7 --warmup 1 --cpu-seconds 0 --no-extras --min-seconds 0"
 prof() { # prefix, workload args..., then the counters come from the caller
   name=$1; shift
   note "$name: kernel trace"
-  rocprofv3 --kernel-trace --stats -d "$out/${tag}_${name}_stats" -o run -- python3 bench.py --steps 7 --warmup 1 --cpu-seconds 0 --no-extras --min-seconds 0 "$@" \
+  rocprofv3 --kernel-trace --stats -d "$out/${tag}_${name}_stats" -o run -- python3 bench.py --full --steps 7 --warmup 1 --cpu-seconds 0 --no-extras --min-seconds 0 "$@" \
       > "$sum/${tag}_${name}_bench_under_rocprof.json" 2> "$out/${tag}_${name}_stats.log"
 }
 pmc() { # name, dir suffix, counters..., -- workload args
@@ -25,7 +25,7 @@ pmc() { # name, dir suffix, counters..., -- workload args
   while [ "$1" != "--" ]; do ctrs+=("$1"); shift; done
   shift
   note "$name: pmc ${ctrs[*]}"
-  rocprofv3 --pmc "${ctrs[@]}" -d "$out/${tag}_${name}_pmc_${sfx}" -o run -- python3 bench.py --steps 7 --warmup 1 --cpu-seconds 0 --no-extras --min-seconds 0 "$@" \
+  rocprofv3 --pmc "${ctrs[@]}" -d "$out/${tag}_${name}_pmc_${sfx}" -o run -- python3 bench.py --full --steps 7 --warmup 1 --cpu-seconds 0 --no-extras --min-seconds 0 "$@" \
       > /dev/null 2> "$out/${tag}_${name}_pmc_${sfx}.log"
 }
 # PARTS=a: C3 + C2 + C4 + default limit + sparse ids + doc shards; PARTS=b: C5 (two gpurun calls of <= 20 min each)
@@ -45,7 +45,7 @@ python3 tools/pmc_summary.py --stats "$out/${tag}_c3_stats" --pmc "$out/${tag}_c
 # made (stamped with the hash of the kernel sources: bench.py refuses a summary of other kernels)
 cp "$sum/${tag}_pmc_summary.json" profiles/ 2>/dev/null
 note "default bench"
-python3 bench.py > "$sum/${tag}_bench.json" 2> "$out/${tag}_bench.err"
+python3 bench.py --full > "$sum/${tag}_bench.json" 2> "$out/${tag}_bench.err"
 
 # (3) the other configurations
 for w in C2 C4; do
@@ -58,19 +58,19 @@ for w in C2 C4; do
       --docs $([ $w = C2 ] && echo 1000000 || echo 10000000) --terms $([ $w = C2 ] && echo 100000 || echo 1000000) \
       --calib "$out/${tag}_pmc_calib" --calib-json "$sum/${tag}_pmc_calib.json"
   cp "$sum/${tag}_${lw}_pmc_summary.json" profiles/ 2>/dev/null
-  python3 bench.py --workload $w --cpu-seconds 10 > "$sum/${tag}_${lw}_bench.json" 2>> "$out/${tag}_bench.err"
+  python3 bench.py --full --workload $w --cpu-seconds 10 > "$sum/${tag}_${lw}_bench.json" 2>> "$out/${tag}_bench.err"
 done
 # C2 with the plan cache on (the loop's query strings repeat: planning becomes a hash lookup)
-python3 bench.py --workload C2 --plan-cache --cpu-seconds 0 --no-extras > "$sum/${tag}_c2_plancache_bench.json" 2>> "$out/${tag}_bench.err"
+python3 bench.py --full --workload C2 --plan-cache --cpu-seconds 0 --no-extras > "$sum/${tag}_c2_plancache_bench.json" 2>> "$out/${tag}_bench.err"
 # the default limit (params == NULL => 1000): MODE_BIG kernels + k_replay_coop
 prof l1000 --limit 1000
 python3 tools/pmc_summary.py --stats "$out/${tag}_l1000_stats" --steps 8 --out-prefix "$sum/${tag}_l1000" --command "$B --limit 1000" --limit 1000
 # sparse random u64 doc ids
 note "sparse ids"
-python3 bench.py --sparse-ids --cpu-seconds 10 --no-extras > "$sum/${tag}_sparse_ids_bench.json" 2>> "$out/${tag}_bench.err"
+python3 bench.py --full --sparse-ids --cpu-seconds 10 --no-extras > "$sum/${tag}_sparse_ids_bench.json" 2>> "$out/${tag}_bench.err"
 # doc shards (N4) on one GPU
 note "doc shards"
-python3 bench.py --docshard 4 --steps 10 --warmup 2 --cpu-seconds 10 > "$sum/${tag}_docshard4_c3_bench.json" 2>> "$out/${tag}_bench.err"
+python3 bench.py --full --docshard 4 --steps 10 --warmup 2 --cpu-seconds 10 > "$sum/${tag}_docshard4_c3_bench.json" 2>> "$out/${tag}_bench.err"
 fi
 if [ "${PARTS#*b}" != "$PARTS" ]; then
 # C5 on one GPU: bench line, kernel stats, traffic (the calibration of part a is reused if its summary is there)
@@ -85,8 +85,8 @@ python3 tools/pmc_summary.py --stats "$out/${tag}_c5_stats" --pmc "$out/${tag}_c
     --steps 8 --out-prefix "$sum/${tag}_c5" --command "$B --workload C5" --name C5 --docs 50000000 --terms 2000000 --batch 8192 \
     --calib "$out/${tag}_pmc_calib" --calib-json "$sum/${tag}_pmc_calib.json"
 cp "$sum/${tag}_c5_pmc_summary.json" profiles/ 2>/dev/null
-python3 bench.py --workload C5 --steps 8 --warmup 2 --cpu-seconds 10 --no-extras > "$sum/${tag}_c5_1gpu_bench.json" 2>> "$out/${tag}_bench.err"
-python3 bench.py --workload C5 --docshard 4 --steps 5 --warmup 1 --cpu-seconds 0 > "$sum/${tag}_docshard4_c5_bench.json" 2>> "$out/${tag}_bench.err"
+python3 bench.py --full --workload C5 --steps 8 --warmup 2 --cpu-seconds 10 --no-extras > "$sum/${tag}_c5_1gpu_bench.json" 2>> "$out/${tag}_bench.err"
+python3 bench.py --full --workload C5 --docshard 4 --steps 5 --warmup 1 --cpu-seconds 0 > "$sum/${tag}_docshard4_c5_bench.json" 2>> "$out/${tag}_bench.err"
 fi
 # the raw rocpd databases are ~10 MB each: gpurun merges at most 64 MiB back
 rm -rf "$out/${tag}"_*_stats "$out/${tag}"_*_pmc_* "$out/${tag}_pmc_calib"
