@@ -171,8 +171,20 @@ nxs_index_t *	nxs_index_open_files(nxs_t *, const char *terms_path,
  * runs a batch on every shard (each on its own device, `device` < 0 = the
  * NXS_GPU_DEVICE default) and merges the shards' candidates through one more
  * exact heap replay: the responses equal those of the unsharded index, ties
- * included.  limit <= 8000, at most 32 query terms; a shard is a static snapshot (no re-sync).  The
- * shards' passes run concurrently (every shard has its own device / streams).
+ * included.  limit <= 8000, at most 32 query terms.  The shards' passes run concurrently (every
+ * shard has its own device / streams).
+ *
+ * A shard serves a static snapshot until the collection is refreshed, explicitly,
+ * between batches: nxs_docshard_refresh() (all shards of the process, as passed to
+ * nxs_docshard_search_batch) or nxs_docshard_refresh_rank() (collective, one process
+ * per shard).  Every shard consumes the files up to ONE snapshot; appended docs go
+ * to the last shard, a removal to the shard that holds the doc, new terms to every
+ * dictionary; every shard's impacts are recomputed once with the collection-wide df.
+ * A re-used or out-of-order doc id, or replaced files, rebuild every shard's slice.
+ * Returns 1: the collection serves the new snapshot; 0: nothing had moved; -1: error
+ * (nxs_get_error; the rank form: the same value on every rank).  A failure after
+ * some shard's device state changed marks the collection inconsistent: searches
+ * fail with NXS_ERR_FATAL until a refresh succeeds.
  *
  * One process per shard (one GPU each): rank r opens shard r of W, attaches a
  * communicator of W ranks (nxs_index_shard), joins the collection
@@ -191,6 +203,8 @@ int		nxs_docshard_attach(nxs_index_t *shard);
 int		nxs_docshard_search_batch_rank(nxs_index_t *shard, nxs_params_t *,
 		    const char *const *queries, size_t n,
 		    nxs_resp_t **resps, nxs_err_t *errs);
+int		nxs_docshard_refresh(nxs_index_t *const *shards, unsigned n_shards);
+int		nxs_docshard_refresh_rank(nxs_index_t *shard);
 
 /* (test hooks and the bench's accessors -- nxs_index_host_profile, nxs_index_device, nxs_test_* -- are
  * not part of this ABI: nxsearch_amd/csrc/nxs_hooks.h, builds with -DNXS_TEST_HOOKS only) */

@@ -164,10 +164,14 @@ typedef struct {
 	uint64_t	n_dead_pairs;
 	uint32_t	hdr_doc_count;	/* header counters now (dtmap.c:660-677) */
 	uint64_t	hdr_token_count;
+	/* doc shards (N4): merge only; the impacts wait for the collection-wide df
+	 * of the new term count (nxsgpu_index_set_global_df) and are computed once */
+	int		defer_impacts;
 } nxsgpu_index_delta_t;
 
-/* merge the delta into the device CSR and recompute every impact; 0 / -1 (the
- * index is unchanged on failure unless the error says otherwise) */
+/* merge the delta into the device CSR and recompute every impact (unless
+ * deferred); 0 / -1 (the index is unchanged on failure unless the error says
+ * otherwise) */
 int		nxsgpu_index_apply(nxsgpu_index_t *, const nxsgpu_index_delta_t *);
 /* replace the BK-tree image (after terms were inserted on the host) */
 int		nxsgpu_index_set_bk(nxsgpu_index_t *, const nxsgpu_bknode_t *nodes, uint32_t n,
@@ -184,6 +188,8 @@ int		nxsgpu_index_set_bk(nxsgpu_index_t *, const nxsgpu_bknode_t *nodes, uint32_
  * (nxsgpu_merge_candidates): identical top-k, ties included.
  */
 int		nxsgpu_index_set_global_df(nxsgpu_index_t *, const uint32_t *df, uint32_t n_terms);
+/* full impact passes since the index was built (each recomputes every impact) */
+uint64_t	nxsgpu_index_impact_passes(const nxsgpu_index_t *);
 /* ids/scores [n_queries][cap], counts [n_queries] (host); counts[q] > cap = overflow */
 int		nxsgpu_search_candidates(nxsgpu_index_t *, int algo, uint64_t limit,
 		    const nxsgpu_query_t *queries, uint32_t n_queries, uint32_t cap,

@@ -88,6 +88,7 @@ NXS_H_SYMBOLS = [
     "nxs_index_shard_local", "nxs_index_shard_slice",
     "nxs_index_open_shard", "nxs_docshard_search_batch",
     "nxs_docshard_attach", "nxs_docshard_search_batch_rank",
+    "nxs_docshard_refresh", "nxs_docshard_refresh_rank",
 ]
 # csrc/nxs_hooks.h: test hooks + bench accessors, only in builds with -DNXS_TEST_HOOKS (the default)
 NXS_HOOK_SYMBOLS = ["nxs_index_device", "nxs_index_host_profile", "nxs_index_shard_info", "nxs_test_pool", "nxs_test_assemble",
@@ -105,7 +106,7 @@ NXS_GPU_H_SYMBOLS = [
     "nxsgpu_index_set_comm", "nxsgpu_batch_begin", "nxsgpu_batch_end",
     "nxsgpu_batches_in_flight", "nxsgpu_index_reconfigure", "nxsgpu_index_set_parallel", "nxsgpu_hbm_read_gbs",
     "nxsgpu_hbm_calibrate",
-    "nxsgpu_index_apply", "nxsgpu_index_set_bk", "nxsgpu_index_set_global_df",
+    "nxsgpu_index_apply", "nxsgpu_index_set_bk", "nxsgpu_index_set_global_df", "nxsgpu_index_impact_passes",
     "nxsgpu_search_candidates", "nxsgpu_merge_candidates",
 ]
 
@@ -392,6 +393,64 @@ class Nxs:
             if p:
                 L.nxs_params_release(p)
         return outs
+
+    def docshard_refresh(self, shards):
+        """nxs_docshard_refresh(): every shard of the collection follows the files to
+        one snapshot.  -> True if anything had moved."""
+        L = lib()
+        L.nxs_docshard_refresh.argtypes = [C.POINTER(C.c_void_p), C.c_uint]
+        hs = (C.c_void_p * len(shards))(*[s._h for s in shards])
+        r = L.nxs_docshard_refresh(hs, len(shards))
+        if r < 0:
+            self._raise()
+        return r == 1
+
+    def docshard_refresh_rank(self, shard):
+        """nxs_docshard_refresh_rank(): collective; this rank's shard follows the files."""
+        L = lib()
+        L.nxs_docshard_refresh_rank.argtypes = [C.c_void_p]
+        r = L.nxs_docshard_refresh_rank(shard._h)
+        if r < 0:
+            self._raise()
+        return r == 1
+
+    def docshard_emulated_refresh(self, shards, after_record=None):
+        """tests: nxs_docshard_refresh_rank() with the ranks played one after the other on
+        this GPU and the collectives done here -- every rank's snapshot record
+        (after_record(rank) runs after each), every rank's merge and df block, every
+        rank's impact pass on the gathered blocks, every rank's outcome.  -> the value
+        each rank returns (1 / 0 / -1)."""
+        L = lib()
+        vp = C.c_void_p
+        u64p = C.POINTER(C.c_uint64)
+        L.nxs_test_docshard_refresh_record.argtypes = [vp, u64p]
+        L.nxs_test_docshard_refresh_merge.argtypes = [vp, u64p, C.c_uint, C.POINTER(C.POINTER(C.c_uint8)),
+                                                      C.POINTER(C.c_size_t)]
+        L.nxs_test_docshard_refresh_finish.restype = C.c_uint32
+        L.nxs_test_docshard_refresh_finish.argtypes = [vp, C.c_char_p, C.c_uint, C.c_size_t]
+        L.nxs_test_docshard_refresh_settle.argtypes = [vp, C.POINTER(C.c_uint32), C.c_uint]
+        libc = C.CDLL(None)
+        libc.free.argtypes = [C.c_void_p]
+        W = len(shards)
+        recs = (C.c_uint64 * (8 * W))()
+        for r, sh in enumerate(shards):
+            L.nxs_test_docshard_refresh_record(sh._h, C.cast(C.byref(recs, 8 * 8 * r), u64p))
+            if after_record:
+                after_record(r)
+        rets, blocks = [], []
+        for sh in shards:
+            blk, ln = C.POINTER(C.c_uint8)(), C.c_size_t()
+            rets.append(L.nxs_test_docshard_refresh_merge(sh._h, recs, W, C.byref(blk), C.byref(ln)))
+            blocks.append(C.string_at(blk, ln.value) if blk else b"")
+            libc.free(blk)
+        if any(x <= 0 for x in rets):
+            assert len(set(rets)) == 1, rets       # the agreement is the same on every rank
+            return rets
+        assert len(set(len(b) for b in blocks)) == 1
+        gathered = b"".join(blocks)
+        fin = (C.c_uint32 * W)(*[L.nxs_test_docshard_refresh_finish(sh._h, gathered, W, len(blocks[0]))
+                                 for sh in shards])
+        return [L.nxs_test_docshard_refresh_settle(sh._h, fin, W) for sh in shards]
 
     def shard_unique_id(self):
         """nxs_shard_unique_id(): the bytes rank 0 hands to the other ranks."""

@@ -3152,6 +3152,14 @@ docshard_search(nxs_index_t *const *local, unsigned n_local, unsigned n_shards, 
 		nxs_decl_err(nxs, NXS_ERR_LIMIT, "doc-sharded search takes limit <= %d", NXSGPU_BIG_K);
 		return -1;
 	}
+	for (unsigned s = 0; s < n_local; s++) {
+		/* (rank form: every rank carries the mark, so none enters the collective) */
+		if (local[s]->ds_inconsistent) {
+			nxs_decl_err(nxs, NXS_ERR_FATAL, "the doc-sharded collection is inconsistent after a failed "
+			    "refresh: refresh it (nxs_docshard_refresh)");
+			return -1;
+		}
+	}
 	/* a shard's heap accepts ~ k (1 + ln(matches / k)) items: room for that from the start (a log that
 	 * overflows costs a second pass over every shard) */
 	if (!cap0 && sp.limit > NXSGPU_FAST_K) {
@@ -3442,6 +3450,420 @@ nxs_docshard_search_batch_rank(nxs_index_t *shard, nxs_params_t *params,
 	return docshard_search(local, 1, shard->n_shards, shard->shard, params, queries, n, resps, errs, 0, NULL, NULL, NULL);
 }
 
+/* ---- N4: following the files (nxs_docshard_refresh[_rank]) ------------------------ */
+
+/*
+ * The record every rank contributes to a refresh (u64 words): its snapshot of the
+ * files, the highest doc id it holds, whether it could take part at all and
+ * whether it carries the "inconsistent" mark of a failed refresh.
+ */
+enum { DSR_TERMS, DSR_DTMAP, DSR_DOCS, DSR_TOKENS, DSR_MAXID, DSR_STATUS, DSR_REBUILD, DSR_WORDS = 8 };
+
+static void
+dsr_record(nxs_index_t *idx, uint64_t rec[DSR_WORDS])
+{
+	nxs_snap_t sn;
+
+	memset(rec, 0, DSR_WORDS * sizeof(uint64_t));
+	if (!idx->tmap || !idx->dmap || !idx->dev) {
+		rec[DSR_STATUS] = NXS_ERR_FATAL;
+		return;
+	}
+	nxs_index_snapshot(idx, &sn);
+	rec[DSR_TERMS] = sn.terms_len;
+	rec[DSR_DTMAP] = sn.dtmap_len;
+	rec[DSR_DOCS] = sn.hdr_docs;
+	rec[DSR_TOKENS] = sn.hdr_tokens;
+	rec[DSR_MAXID] = idx->n_ord ? idx->h_doc_ids[idx->n_ord - 1] : 0;
+	rec[DSR_REBUILD] = idx->ds_inconsistent;
+}
+
+static const uint64_t *
+dsr_consumed(const nxs_index_t *idx, uint64_t c[4])
+{
+	c[0] = idx->terms_consumed;
+	c[1] = idx->dt_consumed;
+	c[2] = idx->hdr_docs_seen;
+	c[3] = idx->hdr_tokens_seen;
+	return c;
+}
+
+/*
+ * Rank protocol, step 1, on the gathered records (a pure function: every rank
+ * computes the same answer).  The snapshot is the record with the largest
+ * nxsdtmap length, the lowest rank on ties -- the ranks share the files, so by
+ * now every rank's view reaches at least that far; the collection's highest doc
+ * id is the largest any rank holds.  -1: a rank could not take part; 0: no
+ * record differs from what was consumed (`consumed`: terms, dtmap, docs, tokens)
+ * and no rank is marked inconsistent; 1: refresh to `out`
+ * (out[DSR_REBUILD]: a full rebuild is due).
+ */
+static int
+dsr_agree(const uint64_t *recs, unsigned W, const uint64_t consumed[4], uint64_t out[DSR_WORDS])
+{
+	unsigned best = 0;
+	uint64_t max_id = 0;
+	bool moved = false, rebuild = false;
+
+	for (unsigned r = 0; r < W; r++) {
+		const uint64_t *x = recs + (size_t)r * DSR_WORDS;
+
+		if (x[DSR_STATUS]) {
+			return -1;
+		}
+		if (x[DSR_DTMAP] > recs[(size_t)best * DSR_WORDS + DSR_DTMAP]) {
+			best = r;
+		}
+		for (unsigned w = 0; w < 4; w++) {
+			moved = moved || x[w] != consumed[w];
+		}
+		rebuild = rebuild || x[DSR_REBUILD];
+		max_id = x[DSR_MAXID] > max_id ? x[DSR_MAXID] : max_id;
+	}
+	memcpy(out, recs + (size_t)best * DSR_WORDS, DSR_WORDS * sizeof(uint64_t));
+	out[DSR_MAXID] = max_id;
+	out[DSR_REBUILD] = rebuild;
+	return moved || rebuild ? 1 : 0;
+}
+
+static void
+dsr_snap(const uint64_t agreed[DSR_WORDS], nxs_snap_t *sn)
+{
+	sn->terms_len = agreed[DSR_TERMS];
+	sn->dtmap_len = agreed[DSR_DTMAP];
+	sn->hdr_docs = agreed[DSR_DOCS];
+	sn->hdr_tokens = agreed[DSR_TOKENS];
+}
+
+/* a shard's host walk to the agreed snapshot: 0 delta in *rd, 1 rebuild, -1 error */
+static int
+dsr_walk(nxs_index_t *idx, const uint64_t agreed[DSR_WORDS], nxs_delta_t **rd)
+{
+	nxs_snap_t sn;
+
+	dsr_snap(agreed, &sn);
+	/* appended docs (ids above every loaded one) go to the last shard */
+	return nxs_shard_walk(idx, &sn, agreed[DSR_MAXID], idx->shard + 1 >= idx->n_shards, rd);
+}
+
+/* a shard's device step: merge its delta (impacts deferred), or with rd == NULL
+ * rebuild its slice of the agreed snapshot; 0 / -1 */
+static int
+dsr_device_step(nxs_index_t *idx, const uint64_t agreed[DSR_WORDS], nxs_delta_t *rd)
+{
+	nxs_snap_t sn;
+
+	if (idx->test_fail_dsref && --idx->test_fail_dsref == 0) {
+		nxs_delta_abort(idx, rd);
+		nxs_decl_err(idx->nxs, NXS_ERR_FATAL, "shard %u: injected failure of the refresh's device step", idx->shard);
+		return -1;
+	}
+	if (rd) {
+		return nxs_shard_merge(idx, rd);
+	}
+	dsr_snap(agreed, &sn);
+	return nxs_shard_rebuild(idx, &sn);
+}
+
+/*
+ * In-process form: all shards of the collection.  One snapshot (four loads,
+ * shard 0's mapping); every shard walks and validates on the host before any
+ * device state changes; then every shard merges (or, if any shard needs it,
+ * every shard rebuilds its slice); then the collection-wide df is summed and
+ * every shard's impacts are recomputed once.  A failure after the first device
+ * step marks the collection inconsistent.
+ */
+int
+nxs_docshard_refresh(nxs_index_t *const *shards, unsigned n_shards)
+{
+	nxs_t *nxs;
+	uint64_t *recs = NULL, agreed[DSR_WORDS], consumed[4];
+	nxs_delta_t **deltas = NULL;
+	bool rebuild;
+	int r, ret = -1;
+
+	if (!shards || n_shards == 0 || !shards[0]) {
+		return -1;
+	}
+	nxs = shards[0]->nxs;
+	nxs_clear_error(nxs);
+	for (unsigned s = 0; s < n_shards; s++) {
+		if (!shards[s] || shards[s]->n_shards != n_shards || shards[s]->shard != s) {
+			nxs_decl_err(nxs, NXS_ERR_INVALID, "the indexes are not shards 0..%u of one collection", n_shards - 1);
+			return -1;
+		}
+		if (pend_oldest(shards[s])) {
+			nxs_decl_err(nxs, NXS_ERR_INVALID, "batches are in flight");
+			return -1;
+		}
+	}
+	recs = calloc((size_t)n_shards * DSR_WORDS, sizeof(uint64_t));
+	deltas = calloc(n_shards, sizeof(*deltas));
+	if (!recs || !deltas) {
+		nxs_decl_err(nxs, NXS_ERR_SYSTEM, "out of memory");
+		goto out;
+	}
+	dsr_record(shards[0], recs);		/* the snapshot: read once */
+	for (unsigned s = 1; s < n_shards; s++) {
+		uint64_t *x = recs + (size_t)s * DSR_WORDS;
+		memcpy(x, recs, DSR_MAXID * sizeof(uint64_t));
+		x[DSR_MAXID] = shards[s]->n_ord ? shards[s]->h_doc_ids[shards[s]->n_ord - 1] : 0;
+		x[DSR_STATUS] = recs[DSR_STATUS];
+		x[DSR_REBUILD] = shards[s]->ds_inconsistent;
+	}
+	if ((r = dsr_agree(recs, n_shards, dsr_consumed(shards[0], consumed), agreed)) <= 0) {
+		if (r < 0) {
+			nxs_decl_err(nxs, NXS_ERR_FATAL, "a shard holds no snapshot");
+		}
+		ret = r;
+		goto out;
+	}
+	rebuild = agreed[DSR_REBUILD] != 0;
+	for (unsigned s = 0; s < n_shards && !rebuild; s++) {
+		if ((r = dsr_walk(shards[s], agreed, &deltas[s])) < 0) {
+			goto fail;	/* (the dictionaries of the shards before it moved on) */
+		}
+		rebuild = r == 1;
+	}
+	for (unsigned s = 0; s < n_shards; s++) {
+		nxs_delta_t *rd = rebuild ? NULL : deltas[s];
+
+		if (rebuild) {
+			nxs_delta_abort(shards[s], deltas[s]);
+		}
+		deltas[s] = NULL;
+		if (dsr_device_step(shards[s], agreed, rd) != 0) {
+			goto fail;
+		}
+	}
+	for (unsigned s = 1; s < n_shards; s++) {
+		if (shards[s]->dt_consumed != shards[0]->dt_consumed) {
+			/* a rebuild stopped at different blocks (one names a term nxsterms does not hold yet) */
+			nxs_decl_err(nxs, NXS_ERR_FATAL, "the shards consumed different parts of the dtmap index");
+			goto fail;
+		}
+	}
+	if (docshard_set_global_df(shards, n_shards) != 0) {
+		goto fail;
+	}
+	for (unsigned s = 0; s < n_shards; s++) {
+		shards[s]->ds_inconsistent = false;
+	}
+	ret = 1;
+	goto out;
+fail:
+	for (unsigned s = 0; s < n_shards; s++) {
+		nxs_delta_abort(shards[s], deltas[s]);
+		deltas[s] = NULL;
+		shards[s]->ds_inconsistent = true;
+	}
+	if (nxs->errcode == NXS_ERR_SUCCESS) {
+		nxs_decl_err(nxs, NXS_ERR_FATAL, "doc-shard refresh failed");
+	}
+out:
+	free(recs);
+	free(deltas);
+	return ret;
+}
+
+/*
+ * Rank form, the phases between the collectives (the test hooks play them one
+ * rank after another).  The block a rank hands to the df all-gather:
+ * u32 status | u32 mode (1 merged, 2 rebuilt) | u32 T | u32 0 | u64 dtmap consumed |
+ * u64 0 | u32 df[cap], cap = agreed nxsterms length / 16 + 2 (a term block takes at
+ * least 16 bytes: every rank's T fits, and every rank knows the size).
+ */
+#define	DSB_HDR	32
+
+static size_t
+dsb_bytes(const uint64_t agreed[DSR_WORDS])
+{
+	return DSB_HDR + (agreed[DSR_TERMS] / 16 + 2) * 4;
+}
+
+/* step 1 -> step 3: agree, walk, device merge (impacts deferred), this rank's block.
+ * -1: a rank could not take part (every rank returns -1); 0: nothing moved; 1: *blk */
+static int
+dsr_merge_phase(nxs_index_t *idx, const uint64_t *recs, unsigned W, uint8_t **blk, size_t *len)
+{
+	uint64_t agreed[DSR_WORDS], consumed[4];
+	nxs_delta_t *rd = NULL;
+	uint32_t *h;
+	int r, mode;
+
+	*blk = NULL;
+	*len = 0;
+	if ((r = dsr_agree(recs, W, dsr_consumed(idx, consumed), agreed)) <= 0) {
+		if (r < 0) {
+			nxs_decl_err(idx->nxs, NXS_ERR_FATAL, "a shard could not take part in the refresh");
+		}
+		return r;
+	}
+	*len = dsb_bytes(agreed);
+	if ((*blk = calloc(1, *len)) == NULL) {
+		nxs_decl_err(idx->nxs, NXS_ERR_SYSTEM, "out of memory");
+		return -1;
+	}
+	h = (uint32_t *)*blk;
+	mode = agreed[DSR_REBUILD] ? 2 : 1;
+	if (mode == 1 && (r = dsr_walk(idx, agreed, &rd)) != 0) {
+		mode = r == 1 ? 2 : 0;
+	}
+	if (mode == 0 || dsr_device_step(idx, agreed, mode == 1 ? rd : NULL) != 0) {
+		h[0] = NXS_ERR_FATAL;		/* still takes part: every rank learns of it */
+		return 1;
+	}
+	if ((size_t)idx->last_id + 2 > (*len - DSB_HDR) / 4) {
+		nxs_decl_err(idx->nxs, NXS_ERR_FATAL, "shard %u: %u terms beyond the snapshot", idx->shard, idx->last_id);
+		h[0] = NXS_ERR_FATAL;
+		return 1;
+	}
+	h[1] = (uint32_t)mode;
+	h[2] = idx->last_id;
+	memcpy(*blk + 16, &idx->dt_consumed, 8);
+	(void)nxsgpu_index_df(idx->dev, (uint32_t *)(*blk + DSB_HDR));
+	return 1;
+}
+
+/* step 3 -> 4: every rank's block; the summed df, one impact pass.  0, or the failure
+ * this rank reports to the final exchange */
+static uint32_t
+dsr_finish(nxs_index_t *idx, const uint8_t *all, unsigned W, size_t len)
+{
+	const uint32_t *h0 = (const uint32_t *)all;
+	const uint32_t T = h0[2];
+	uint32_t *sum;
+
+	for (unsigned r = 0; r < W; r++) {
+		const uint8_t *b = all + (size_t)r * len;
+		const uint32_t *h = (const uint32_t *)b;
+
+		if (h[0] || h[1] != h0[1] || h[2] != T || memcmp(b + 16, all + 16, 8) != 0) {
+			if (idx->nxs->errcode == NXS_ERR_SUCCESS) {
+				nxs_decl_err(idx->nxs, NXS_ERR_FATAL, h[0] ? "shard %u failed its part of the refresh" :
+				    "shard %u reached a different state in the refresh", r);
+			}
+			return NXS_ERR_FATAL;
+		}
+	}
+	if (T != idx->last_id || (sum = calloc((size_t)T + 2, sizeof(uint32_t))) == NULL) {
+		nxs_decl_err(idx->nxs, NXS_ERR_FATAL, "shard %u: the collection-wide df does not fit", idx->shard);
+		return NXS_ERR_FATAL;
+	}
+	for (unsigned r = 0; r < W; r++) {
+		const uint32_t *df = (const uint32_t *)(all + (size_t)r * len + DSB_HDR);
+		for (uint32_t t = 1; t <= T; t++) {
+			sum[t] += df[t];
+		}
+	}
+	if (nxsgpu_index_set_global_df(idx->dev, sum, T) != 0) {
+		nxs_decl_err(idx->nxs, NXS_ERR_FATAL, "shard %u: %s", idx->shard, nxsgpu_last_error());
+		free(sum);
+		return NXS_ERR_FATAL;
+	}
+	free(sum);
+	idx->global_df_set = true;
+	return 0;
+}
+
+/* after the final exchange of the ranks' finish status: 1 all done, -1 marked inconsistent */
+static int
+dsr_settle(nxs_index_t *idx, const uint32_t *fin, unsigned W)
+{
+	for (unsigned r = 0; r < W; r++) {
+		if (fin[r]) {
+			idx->ds_inconsistent = true;
+			if (idx->nxs->errcode == NXS_ERR_SUCCESS) {
+				nxs_decl_err(idx->nxs, NXS_ERR_FATAL, "shard %u failed the refresh: the collection is "
+				    "inconsistent until the next refresh", r);
+			}
+			return -1;
+		}
+	}
+	idx->ds_inconsistent = false;
+	return 1;
+}
+
+/*
+ * One process per shard (collective over the communicator of nxs_index_shard):
+ * all-gather of the snapshot records (the only collective when nothing moved),
+ * agree + walk + merge, all-gather of the df blocks (with each rank's status),
+ * one impact pass with the summed df, all-gather of the outcome.  Every rank
+ * returns the same value.
+ */
+static int
+dsr_gather(nxs_index_t *idx, const void *mine, void *all, size_t len)
+{
+	if (idx->n_shards <= 1) {
+		memcpy(all, mine, len);
+		return 0;
+	}
+	if (nxsgpu_comm_allgather(idx->comm, mine, all, len) != 0) {
+		nxs_decl_err(idx->nxs, NXS_ERR_FATAL, "all-gather failed: %s", nxsgpu_last_error());
+		return -1;
+	}
+	return 0;
+}
+
+int
+nxs_docshard_refresh_rank(nxs_index_t *shard)
+{
+	nxs_t *nxs = shard->nxs;
+	const unsigned W = shard->n_shards > 1 ? shard->n_shards : 1;
+	uint64_t mine[DSR_WORDS], *recs = NULL;
+	uint8_t *blk = NULL, *all = NULL;
+	uint32_t fin, *fins = NULL;
+	size_t len = 0;
+	int r, ret = -1;
+
+	nxs_clear_error(nxs);
+	if (W > 1 && (!shard->comm || nxsgpu_comm_world(shard->comm) != (int)W ||
+	    nxsgpu_comm_rank(shard->comm) != (int)shard->shard)) {
+		nxs_decl_err(nxs, NXS_ERR_INVALID, "shard %u of %u needs a communicator of %u ranks with itself as "
+		    "rank %u (nxs_index_shard)", shard->shard, W, W, shard->shard);
+		return -1;
+	}
+	if (pend_oldest(shard)) {
+		nxs_decl_err(nxs, NXS_ERR_INVALID, "batches are in flight");
+		return -1;
+	}
+	recs = malloc((size_t)W * sizeof(mine));
+	fins = malloc((size_t)W * sizeof(uint32_t));
+	if (!recs || !fins) {
+		nxs_decl_err(nxs, NXS_ERR_SYSTEM, "out of memory");
+		goto out;
+	}
+	dsr_record(shard, mine);
+	if (dsr_gather(shard, mine, recs, sizeof(mine)) != 0) {
+		goto fail;
+	}
+	if ((r = dsr_merge_phase(shard, recs, W, &blk, &len)) <= 0) {
+		ret = r;
+		goto out;
+	}
+	if ((all = malloc(len * W)) == NULL) {
+		nxs_decl_err(nxs, NXS_ERR_SYSTEM, "out of memory");
+		goto fail;
+	}
+	if (dsr_gather(shard, blk, all, len) != 0) {
+		goto fail;
+	}
+	fin = dsr_finish(shard, all, W, len);
+	if (dsr_gather(shard, &fin, fins, sizeof(fin)) != 0) {
+		goto fail;
+	}
+	ret = dsr_settle(shard, fins, W);
+	goto out;
+fail:
+	shard->ds_inconsistent = true;
+out:
+	free(all);
+	free(blk);
+	free(recs);
+	free(fins);
+	return ret;
+}
+
 #ifdef NXS_TEST_HOOKS
 /*
  * Tests (one GPU, no second rank to talk to): the two halves of the rank form.
@@ -3482,6 +3904,52 @@ int
 nxs_test_docshard_set_df(nxs_index_t *const *shards, unsigned n_shards)
 {
 	return docshard_set_global_df(shards, n_shards);
+}
+
+/*
+ * The rank form of nxs_docshard_refresh_rank() with the collectives played by the
+ * caller: _record() = this rank's snapshot record, _merge() = agree on the
+ * gathered records, walk, merge on the device and hand out this rank's df block
+ * (malloc'ed), _finish() = the summed df of the gathered blocks and one impact
+ * pass (-> the status this rank reports), _settle() = the outcome of all ranks.
+ */
+void
+nxs_test_docshard_refresh_record(nxs_index_t *shard, uint64_t rec[8])
+{
+	dsr_record(shard, rec);
+}
+
+int
+nxs_test_docshard_refresh_merge(nxs_index_t *shard, const uint64_t *recs, unsigned W, uint8_t **block, size_t *len)
+{
+	nxs_clear_error(shard->nxs);
+	return dsr_merge_phase(shard, recs, W, block, len);
+}
+
+uint32_t
+nxs_test_docshard_refresh_finish(nxs_index_t *shard, const uint8_t *gathered, unsigned W, size_t len)
+{
+	return dsr_finish(shard, gathered, W, len);
+}
+
+int
+nxs_test_docshard_refresh_settle(nxs_index_t *shard, const uint32_t *fin, unsigned W)
+{
+	return dsr_settle(shard, fin, W);
+}
+
+/* the snapshot-agreement rule of the rank form (pure host function) */
+int
+nxs_test_docshard_agree(const uint64_t *recs, unsigned W, const uint64_t consumed[4], uint64_t out[8])
+{
+	return dsr_agree(recs, W, consumed, out);
+}
+
+/* full impact passes of an index's device side so far */
+uint64_t
+nxs_test_impact_passes(nxs_index_t *idx)
+{
+	return idx->dev ? nxsgpu_index_impact_passes(idx->dev) : 0;
 }
 
 #endif /* NXS_TEST_HOOKS */
@@ -3748,11 +4216,14 @@ nxs_test_pack_abort(uint8_t *block, uint32_t n_slots, uint32_t k, uint32_t code)
 }
 
 /* the n-th next _begin (which = 0) / exact fix-up round (1) of the index fails; 2: the n-th next
- * fix-up round finds no memory for its receive buffer; 3: the n-th next late second half (late_complete) fails */
+ * fix-up round finds no memory for its receive buffer; 3: the n-th next late second half (late_complete) fails;
+ * 4: the n-th next device step (merge or rebuild) of a doc-shard refresh fails */
 void
 nxs_test_inject_failure(nxs_index_t *idx, int which, unsigned nth)
 {
-	if (which == 0) {
+	if (which == 4) {
+		idx->test_fail_dsref = nth;
+	} else if (which == 0) {
 		idx->test_fail_begin = nth;
 	} else if (which == 1) {
 		idx->test_fail_fixup = nth;

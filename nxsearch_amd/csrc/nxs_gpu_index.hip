@@ -889,8 +889,9 @@ rebuild_impacts(nxsgpu_index_t *ix, unsigned only)
 		std::vector<std::thread> thr;
 		auto work = [&](uint32_t lo, uint32_t hi) {
 			for (uint32_t t = lo; t < hi; t++) {
-				/* doc-sharded (N4): df of the WHOLE collection, not of this shard */
-				const unsigned long df = !ix->df_global.empty() ? ix->df_global[t] :
+				/* doc-sharded (N4): df of the WHOLE collection, not of this shard
+				 * (a term the collection-wide array does not cover yet: local) */
+				const unsigned long df = t < ix->df_global.size() ? ix->df_global[t] :
 				    ix->h_post_off[t + 1] - ix->h_post_off[t];
 				if (df == 0 || N == 0) {
 					continue;
@@ -909,6 +910,9 @@ rebuild_impacts(nxsgpu_index_t *ix, unsigned only)
 		for (auto &th : thr) {
 			th.join();
 		}
+	}
+	if (only == 3) {
+		ix->n_impact_passes++;
 	}
 	ix->tfidf_valid = N != 0;
 	ix->bm25_valid = false;
@@ -1539,6 +1543,13 @@ nxsgpu_index_apply(nxsgpu_index_t *ix, const nxsgpu_index_delta_t *d)
 		set_error("hipSetDevice failed");
 		return -1;
 	}
+	if (n_newdocs == 0 && n_dead == 0 && T_new == T_old) {
+		/* nothing to merge (a doc shard whose share of the delta is empty): the
+		 * header counters still move every idf */
+		ix->hdr_doc_count = d->hdr_doc_count;
+		ix->hdr_token_count = d->hdr_token_count;
+		return d->defer_impacts ? 0 : rebuild_impacts(ix);
+	}
 	uint64_t min_off = ~0ull, max_end = 0;
 	for (uint64_t i = 0; i < n_newdocs; i++) {
 		min_off = std::min(min_off, d->blk_off[i]);
@@ -1718,12 +1729,12 @@ nxsgpu_index_apply(nxsgpu_index_t *ix, const nxsgpu_index_delta_t *d)
 		}
 	}
 	t_a2 = now_ms();
-	if (rebuild_impacts(ix) != 0) {
+	if (!d->defer_impacts && rebuild_impacts(ix) != 0) {
 		goto fail;
 	}
 	if (ix->cfg.debug_timing) {
-		fprintf(stderr, "[nxsgpu apply] delta %.1f ms, merge %.1f ms, impacts + columns %.1f ms\n",
-		    t_a1 - t_a0, t_a2 - t_a1, now_ms() - t_a2);
+		fprintf(stderr, "[nxsgpu apply] delta %.1f ms, merge %.1f ms, impacts + columns %.1f ms%s\n",
+		    t_a1 - t_a0, t_a2 - t_a1, now_ms() - t_a2, d->defer_impacts ? " (deferred)" : "");
 	}
 	rc = 0;
 fail:
@@ -1853,6 +1864,8 @@ nxsgpu_index_set_global_df(nxsgpu_index_t *ix, const uint32_t *df, uint32_t n_te
 	}
 	return rebuild_impacts(ix);
 }
+
+extern "C" uint64_t nxsgpu_index_impact_passes(const nxsgpu_index_t *ix) { return ix->n_impact_passes; }
 
 extern "C" void
 nxsgpu_results_free(nxsgpu_results_t *res)

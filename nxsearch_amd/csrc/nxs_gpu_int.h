@@ -258,6 +258,7 @@ struct nxsgpu_index {
 	std::vector<uint64_t> h_post_off;
 	std::vector<float> h_maximp[2];	/* [T+2] largest impact per term and ranking algo */
 	std::vector<uint32_t> df_global;	/* [T+2] doc-sharded mode: collection-wide df, else empty */
+	uint64_t	n_impact_passes = 0;	/* full rebuild_impacts passes (tests: one per doc-shard refresh) */
 	/*
 	 * Dense terms (lists holding more than cfg.scanm_dens of the docs: a few
 	 * dozen at most) also get a direct-access impact COLUMN per ranking

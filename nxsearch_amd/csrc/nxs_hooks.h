@@ -61,6 +61,14 @@ int		nxs_test_docshard_block(nxs_index_t *shard, nxs_params_t *, const char *con
 int		nxs_test_docshard_finish(nxs_index_t *shard, nxs_params_t *, const char *const *queries, size_t n,
 		    uint32_t cap, const uint8_t *gathered, nxs_resp_t **resps, nxs_err_t *errs);
 int		nxs_test_docshard_set_df(nxs_index_t *const *shards, unsigned n_shards);
+/* doc shards: the phases of nxs_docshard_refresh_rank() between its collectives, the agreement rule */
+void		nxs_test_docshard_refresh_record(nxs_index_t *shard, uint64_t rec[8]);
+int		nxs_test_docshard_refresh_merge(nxs_index_t *shard, const uint64_t *recs, unsigned W,
+		    uint8_t **block, size_t *len);
+uint32_t	nxs_test_docshard_refresh_finish(nxs_index_t *shard, const uint8_t *gathered, unsigned W, size_t len);
+int		nxs_test_docshard_refresh_settle(nxs_index_t *shard, const uint32_t *fin, unsigned W);
+int		nxs_test_docshard_agree(const uint64_t *recs, unsigned W, const uint64_t consumed[4], uint64_t out[8]);
+uint64_t	nxs_test_impact_passes(nxs_index_t *);
 
 #endif /* NXS_TEST_HOOKS */
 #endif /* NXS_HOOKS_H */

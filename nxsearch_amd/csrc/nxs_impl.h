@@ -68,6 +68,16 @@ typedef struct {
 
 struct qprep;
 
+/* one snapshot of the two index files: the four words nxs_index_changed() reads
+ * (doc-shard refresh: every shard consumes exactly up to it) */
+typedef struct {
+	uint64_t	terms_len, dtmap_len;	/* data_len of nxsterms / nxsdtmap */
+	uint64_t	hdr_docs, hdr_tokens;	/* nxsdtmap header counters */
+} nxs_snap_t;
+
+/* a doc shard's share of one refresh, walked and validated on the host (nxs_index.c) */
+typedef struct nxs_delta nxs_delta_t;
+
 /* one batch between nxs_index_search_batch_begin and _end */
 typedef struct nxs_pend {
 	bool		active;
@@ -136,6 +146,11 @@ struct nxs_index {
 	unsigned	shard, n_shards;
 	int		want_device;	/* explicit device + 1, or 0: NXS_GPU_DEVICE / device 0 */
 	bool		global_df_set;
+	/* a doc-shard refresh failed after some device state changed: searches are refused
+	 * until the next refresh rebuilds the collection (nxs_docshard_refresh) */
+	bool		ds_inconsistent;
+	unsigned	test_fail_dsref;	/* tests: the n-th next device step of a shard refresh fails */
+	const nxs_snap_t *pin;		/* load / rebuild up to this snapshot (NULL: the file headers) */
 	bool		shard_local;	/* nxs_index_shard_local: responses of the own slice only */
 	int8_t		late_mode;	/* 0 not read yet, 1 a batch's fuzzy pass is left running (late_finish), 2 NXS_LATE_FUZZY=0:
 					 * _begin waits for it itself */
@@ -171,6 +186,12 @@ int	nxs_index_refresh(nxs_index_t *);
 bool	nxs_index_changed(const nxs_index_t *);
 int	nxs_index_bk_sync(nxs_index_t *);
 void	nxs_index_refresh_stats(const nxs_index_t *, uint64_t out[2]);
+/* doc-shard refresh (N4): the pieces of nxs_index_refresh, driven per collection by nxs_api.c */
+void	nxs_index_snapshot(const nxs_index_t *, nxs_snap_t *);
+int	nxs_shard_walk(nxs_index_t *, const nxs_snap_t *, uint64_t max_id, bool take_new, nxs_delta_t **);
+int	nxs_shard_merge(nxs_index_t *, nxs_delta_t *);
+void	nxs_delta_abort(nxs_index_t *, nxs_delta_t *);
+int	nxs_shard_rebuild(nxs_index_t *, const nxs_snap_t *);
 uint32_t nxs_term_lookup(const nxs_index_t *, const uint8_t *val, size_t len);
 
 /* flattened BK-tree built on the host (exported for the CPU-side tests) */

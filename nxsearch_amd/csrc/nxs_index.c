@@ -135,10 +135,11 @@ thash_rebuild(nxs_index_t *idx, size_t cap)
  * [idx->terms_consumed, data_len) of the mapped nxsterms image.  Ids are file
  * order (terms.c:404); a duplicate string keeps its id unused
  * (idxterm_insert => EEXIST, idxterm.c:166-171).  Used by the first load and by
- * every refresh.
+ * every refresh.  `upto`: the data length to consume to (a doc-shard refresh's
+ * agreed snapshot), or UINT64_MAX for the header's.
  */
 static int
-sync_terms(nxs_index_t *idx)
+sync_terms(nxs_index_t *idx, uint64_t upto)
 {
 	const uint8_t *hdr = idx->tmap;
 	size_t data_len, off;
@@ -153,6 +154,13 @@ sync_terms(nxs_index_t *idx)
 		return -1;
 	}
 	data_len = be32toh(__atomic_load_n((const uint32_t *)(hdr + 8), __ATOMIC_ACQUIRE));
+	if (upto != UINT64_MAX) {
+		if (upto > data_len) {
+			nxs_decl_err(idx->nxs, NXS_ERR_FATAL, "corrupted terms index");
+			return -1;	/* the file shrank below the snapshot: replaced */
+		}
+		data_len = upto;
+	}
 	if (TERMS_HDR_LEN + data_len > idx->tmap_len) {
 		/* the reference maps in 32 KiB steps and fails likewise
 		 * (idxmap.c:119-148) */
@@ -523,7 +531,7 @@ static int
 walk_dtmap(nxs_index_t *idx, uint64_t stop_off, ldoc_t **docs_out, uint64_t *n_out)
 {
 	const uint8_t *hdr = idx->dmap;
-	const uint64_t data_len = rd64(hdr + 8);
+	const uint64_t data_len = idx->pin ? idx->pin->dtmap_len : rd64(hdr + 8);
 	ldoc_t *docs = NULL;
 	size_t n = 0, cap = 0;
 	bool ascending = true;
@@ -670,7 +678,7 @@ nxs_index_load(nxs_index_t *idx, const char *terms_path, const char *dtmap_path)
 		return -1;
 	}
 	idx->terms_consumed = 0;
-	if (sync_terms(idx) == -1) {
+	if (sync_terms(idx, idx->pin ? idx->pin->terms_len : UINT64_MAX) == -1) {
 		return -1;
 	}
 	if (idx->dmap_len < DTMAP_HDR_LEN || memcmp(idx->dmap, "NXS_D", 5) != 0) {
@@ -685,6 +693,10 @@ nxs_index_load(nxs_index_t *idx, const char *terms_path, const char *dtmap_path)
 	if (DTMAP_HDR_LEN + rd64(idx->dmap + 8) > idx->dmap_len) {
 		nxs_decl_err(idx->nxs, NXS_ERR_SYSTEM, "dtmap mapping failed");
 		return -1;
+	}
+	if (idx->pin && idx->pin->dtmap_len > rd64(idx->dmap + 8)) {
+		nxs_decl_err(idx->nxs, NXS_ERR_FATAL, "corrupted dtmap index");
+		return -1;	/* the file shrank below the snapshot: replaced */
 	}
 	if ((idx->bktree = nxs_bktree_create()) == NULL ||
 	    nxs_bktree_insert(idx->bktree, idx->terms, 0, idx->last_id) == -1 ||
@@ -705,7 +717,8 @@ nxs_index_load(nxs_index_t *idx, const char *terms_path, const char *dtmap_path)
 	}
 
 	for (int attempt = 0; attempt < 3; attempt++) {
-		const uint64_t data_len = be64toh(__atomic_load_n((const uint64_t *)(idx->dmap + 8), __ATOMIC_ACQUIRE));
+		const uint64_t data_len = idx->pin ? idx->pin->dtmap_len :
+		    be64toh(__atomic_load_n((const uint64_t *)(idx->dmap + 8), __ATOMIC_ACQUIRE));
 		ldoc_t *docs = NULL;
 		uint64_t n = 0, *pair_base, bad;
 		const char *dev_env = getenv("NXS_GPU_DEVICE");
@@ -754,8 +767,8 @@ nxs_index_load(nxs_index_t *idx, const char *terms_path, const char *dtmap_path)
 		src.n_docs = n;
 		src.n_terms = idx->last_id;
 		src.term_ok = term_ok;
-		src.hdr_doc_count = rd32(idx->dmap + 24);	/* dtmap.c:671-677 */
-		src.hdr_token_count = rd64(idx->dmap + 16);	/* dtmap.c:660-666 */
+		src.hdr_doc_count = idx->pin ? (uint32_t)idx->pin->hdr_docs : rd32(idx->dmap + 24);	/* dtmap.c:671-677 */
+		src.hdr_token_count = idx->pin ? idx->pin->hdr_tokens : rd64(idx->dmap + 16);	/* dtmap.c:660-666 */
 		src.bk_nodes = bk.nodes;
 		src.n_bk = bk.n;
 		src.bk_depth = bk.depth;
@@ -877,30 +890,26 @@ remap_if_grown(nxs_index_t *idx)
 	return 0;
 }
 
-/* the whole snapshot again, built beside the old one and swapped in on success */
+/* the whole snapshot again (a doc shard: its slice, up to idx->pin if set),
+ * built beside the old one and swapped in on success; 0 / -1 (old one kept) */
 static int
-refresh_rebuild(nxs_index_t *idx)
+rebuild_snapshot(nxs_index_t *idx)
 {
 	nxs_index_t tmp;
-	const nxs_err_t saved_code = idx->nxs->errcode;
 
 	memset(&tmp, 0, sizeof(tmp));
 	tmp.nxs = idx->nxs;
 	tmp.algo = idx->algo;
 	tmp.lowercase = idx->lowercase;
+	tmp.shard = idx->shard;
+	tmp.n_shards = idx->n_shards;
+	tmp.want_device = idx->want_device;
+	tmp.pin = idx->pin;
 	tmp.terms_path = idx->terms_path;
 	tmp.dtmap_path = idx->dtmap_path;
 	if (nxs_index_load(&tmp, idx->terms_path, idx->dtmap_path) != 0) {
-		/*
-		 * The files cannot be consumed right now (a writer in the middle of
-		 * an append): the old snapshot keeps serving, as the reference's
-		 * partial sync does (dtmap.c:527-535); the next search tries again.
-		 */
 		unload_snapshot(&tmp);
-		if (saved_code == NXS_ERR_SUCCESS) {
-			nxs_clear_error(idx->nxs);
-		}
-		return 0;
+		return -1;
 	}
 	if (idx->comm) {
 		(void)nxsgpu_index_set_comm(idx->dev, NULL);
@@ -933,7 +942,24 @@ refresh_rebuild(nxs_index_t *idx)
 	if (idx->comm) {
 		(void)nxsgpu_index_set_comm(idx->dev, idx->comm);
 	}
+	idx->global_df_set = false;	/* (a doc shard's new device index scores with local df) */
 	idx->n_rebuilds++;
+	return 0;
+}
+
+static int
+refresh_rebuild(nxs_index_t *idx)
+{
+	const nxs_err_t saved_code = idx->nxs->errcode;
+
+	if (rebuild_snapshot(idx) != 0 && saved_code == NXS_ERR_SUCCESS) {
+		/*
+		 * The files cannot be consumed right now (a writer in the middle of
+		 * an append): the old snapshot keeps serving, as the reference's
+		 * partial sync does (dtmap.c:527-535); the next search tries again.
+		 */
+		nxs_clear_error(idx->nxs);
+	}
 	return 0;
 }
 
@@ -989,19 +1015,219 @@ dbg_ms(void)
 	return 1e3 * (double)ts.tv_sec + 1e-6 * (double)ts.tv_nsec;
 }
 
+/* what one refresh consumes beyond the last sync: appended docs, removed docs' postings */
+struct nxs_delta {
+	uint64_t	*nb_off, *nb_ids, *nb_base;	/* appended doc blocks */
+	size_t		n_new, cap_new;
+	uint32_t	*dead_term, *dead_ord;		/* (term, ordinal) of every posting of a removed doc */
+	size_t		n_deadp, cap_deadp;
+	uint32_t	*dead_list;			/* ordinals of the removed docs (h_alive = 2 until commit) */
+	size_t		n_dead, cap_dead;
+	uint64_t	d_now, consumed_to;		/* nxsdtmap data length walked to / consumed to */
+	uint64_t	hd_docs, hd_tokens;		/* header counters of the snapshot */
+};
+
+static void
+delta_release(struct nxs_delta *rd)
+{
+	free(rd->nb_off);
+	free(rd->nb_ids);
+	free(rd->nb_base);
+	free(rd->dead_term);
+	free(rd->dead_ord);
+	free(rd->dead_list);
+	memset(rd, 0, sizeof(*rd));
+}
+
+/* the removed docs are alive again (the delta is not applied) */
+static void
+delta_rollback(nxs_index_t *idx, struct nxs_delta *rd)
+{
+	for (size_t i = 0; i < rd->n_dead; i++) {
+		idx->h_alive[rd->dead_list[i]] = 1;
+	}
+	rd->n_dead = 0;
+}
+
+/*
+ * idx_dtmap_sync over the blocks in [dt_consumed, rd->d_now): 0, or 1 when only
+ * a full rebuild can take them (a re-used or out-of-order id: at or below
+ * `max_id`, the highest doc id of the whole collection; a doc added and removed
+ * within the delta; a torn block).  Appended docs are validated by every
+ * caller alike but kept only when `take_new` (a doc shard other than the last
+ * one leaves them to the last); a tombstone of a doc this index does not hold
+ * is skipped.
+ */
+static int
+delta_walk(nxs_index_t *idx, struct nxs_delta *rd, uint64_t max_id, bool take_new)
+{
+	const uint64_t d_now = rd->d_now;
+	uint64_t off;
+
+	rd->consumed_to = idx->dt_consumed;
+	for (off = idx->dt_consumed; off < d_now; ) {
+		const uint8_t *p = idx->dmap + DTMAP_HDR_LEN + off;
+		const uint64_t remaining = d_now - off;
+		uint64_t doc_id;
+		uint32_t doc_len, np;
+		bool ok = true;
+
+		if (remaining < 16) {
+			return 1;
+		}
+		doc_id = rd64(p);
+		doc_len = rd32(p + 8);
+		np = rd32(p + 12);
+		if ((uint64_t)np * 8 > remaining - 16) {
+			return 1;
+		}
+		if (doc_id == 0) {
+			/* deleted block: dtmap.c:364-367 */
+		} else if (doc_len == 0) {
+			/* tombstone (dtmap.c:374-381): drop the doc if it is loaded */
+			const int64_t o = ord_of(idx, doc_id);
+			bool pending = false;
+
+			for (size_t i = 0; i < rd->n_new && !pending; i++) {
+				pending = rd->nb_ids[i] == doc_id;
+			}
+			if (pending) {
+				return 1;		/* added and removed within one delta */
+			} else if (o >= 0 && idx->h_alive[o]) {
+				const uint8_t *blk = idx->dmap + idx->h_blk_off[o];
+				const uint32_t n = idx->h_npairs[o];
+
+				if (rd->n_dead == rd->cap_dead) {
+					rd->cap_dead = rd->cap_dead ? rd->cap_dead * 2 : 64;
+					rd->dead_list = realloc(rd->dead_list, rd->cap_dead * sizeof(uint32_t));
+				}
+				rd->dead_list[rd->n_dead++] = (uint32_t)o;
+				idx->h_alive[o] = 2;	/* dying: committed by delta_commit */
+				if (rd->n_deadp + n > rd->cap_deadp) {
+					rd->cap_deadp = (rd->n_deadp + n) * 2 + 64;
+					rd->dead_term = realloc(rd->dead_term, rd->cap_deadp * sizeof(uint32_t));
+					rd->dead_ord = realloc(rd->dead_ord, rd->cap_deadp * sizeof(uint32_t));
+				}
+				/* the removed doc's block still holds its pairs (only the doc
+				 * id was zeroed: dtmap.c:603) */
+				for (uint32_t j = 0; j < n; j++) {
+					rd->dead_term[rd->n_deadp] = rd32(blk + 16 + 8 * (size_t)j);
+					rd->dead_ord[rd->n_deadp] = (uint32_t)o;
+					rd->n_deadp++;
+				}
+			}
+		} else {
+			const int64_t o = ord_of(idx, doc_id);
+
+			if (doc_id <= max_id || (o >= 0 && idx->h_alive[o])) {
+				return 1;		/* out-of-order or re-used id */
+			}
+			/* every pair must name a visible, live term: else stop here
+			 * (partial sync, dtmap.c:406-413,527-535) */
+			for (uint32_t j = 0; j < np && ok; j++) {
+				const uint32_t tid = rd32(p + 16 + 8 * (size_t)j);
+				ok = tid != 0 && tid <= idx->last_id && idx->terms[tid].tot_off != 0;
+			}
+			if (!ok) {
+				break;
+			}
+			if (rd->n_new == rd->cap_new) {
+				rd->cap_new = rd->cap_new ? rd->cap_new * 2 : 64;
+				rd->nb_off = realloc(rd->nb_off, rd->cap_new * sizeof(uint64_t));
+				rd->nb_ids = realloc(rd->nb_ids, rd->cap_new * sizeof(uint64_t));
+				rd->nb_base = realloc(rd->nb_base, (rd->cap_new + 1) * sizeof(uint64_t));
+			}
+			if (rd->n_new == 0) {
+				rd->nb_base[0] = 0;
+			}
+			rd->nb_off[rd->n_new] = DTMAP_HDR_LEN + off;
+			rd->nb_ids[rd->n_new] = doc_id;
+			rd->nb_base[rd->n_new + 1] = rd->nb_base[rd->n_new] + np;
+			rd->n_new++;
+			max_id = doc_id;
+		}
+		off += 16 + (uint64_t)np * 8;
+		rd->consumed_to = off;
+	}
+	if (!take_new) {
+		rd->n_new = 0;		/* the last shard takes them */
+	}
+	return idx->n_ord + rd->n_new >= UINT32_MAX - 1 ? 1 : 0;
+}
+
+/* the delta into the device CSR (nxsgpu_index_apply); 0 / -1 */
+static int
+delta_apply(nxs_index_t *idx, const struct nxs_delta *rd, bool defer_impacts)
+{
+	nxsgpu_index_delta_t dl;
+	uint8_t *term_ok = calloc((size_t)idx->last_id + 1, 1);
+	int r;
+
+	if (!term_ok) {
+		nxs_decl_err(idx->nxs, NXS_ERR_SYSTEM, "out of memory");
+		return -1;
+	}
+	for (uint32_t id = 1; id <= idx->last_id; id++) {
+		term_ok[id] = idx->terms[id].tot_off != 0;
+	}
+	memset(&dl, 0, sizeof(dl));
+	dl.n_terms = idx->last_id;
+	dl.term_ok = term_ok;
+	dl.dtmap_img = idx->dmap;
+	dl.dtmap_len = DTMAP_HDR_LEN + rd->d_now;
+	dl.blk_off = rd->nb_off;
+	dl.doc_ids = rd->nb_ids;
+	dl.pair_base = rd->nb_base;
+	dl.n_new = rd->n_new;
+	dl.dead_term = rd->dead_term;
+	dl.dead_ord = rd->dead_ord;
+	dl.n_dead_pairs = rd->n_deadp;
+	dl.hdr_doc_count = (uint32_t)rd->hd_docs;
+	dl.hdr_token_count = rd->hd_tokens;
+	dl.defer_impacts = defer_impacts;
+	r = nxsgpu_index_apply(idx->dev, &dl);
+	free(term_ok);
+	return r;
+}
+
+/* the host tables follow the device: removed docs die, appended docs take the next ordinals */
+static void
+delta_commit(nxs_index_t *idx, const struct nxs_delta *rd)
+{
+	for (size_t i = 0; i < rd->n_dead; i++) {
+		idx->h_alive[rd->dead_list[i]] = 0;
+	}
+	if (idx->n_ord + rd->n_new > idx->cap_ord) {
+		idx->cap_ord = (idx->n_ord + rd->n_new) * 2 + 1024;
+		idx->h_doc_ids = realloc(idx->h_doc_ids, idx->cap_ord * sizeof(uint64_t));
+		idx->h_blk_off = realloc(idx->h_blk_off, idx->cap_ord * sizeof(uint64_t));
+		idx->h_npairs = realloc(idx->h_npairs, idx->cap_ord * sizeof(uint32_t));
+		idx->h_alive = realloc(idx->h_alive, idx->cap_ord);
+	}
+	for (size_t i = 0; i < rd->n_new; i++) {
+		idx->h_doc_ids[idx->n_ord] = rd->nb_ids[i];
+		idx->h_blk_off[idx->n_ord] = rd->nb_off[i];
+		idx->h_npairs[idx->n_ord] = (uint32_t)(rd->nb_base[i + 1] - rd->nb_base[i]);
+		idx->h_alive[idx->n_ord] = 1;
+		idx->n_ord++;
+	}
+	idx->n_docs = idx->n_ord;
+	idx->dt_consumed = rd->consumed_to;
+	idx->hdr_docs_seen = rd->hd_docs;
+	idx->hdr_tokens_seen = rd->hd_tokens;
+	/* term totals moved (dtmap.c:236,626): the "total > 0" flags of the BK image
+	 * and, with new terms, the image itself are brought up to date before the
+	 * next fuzzy search (nxs_index_bk_sync) */
+	idx->bk_flags_stale = true;
+	idx->n_incremental++;
+}
+
 int
 nxs_index_refresh(nxs_index_t *idx)
 {
 	double t_dbg[3] = { dbg_ms(), 0, 0 };
 	uint64_t t_now, d_now, hd_docs, hd_tokens;
-	uint64_t *nb_off = NULL, *nb_ids = NULL, *nb_base = NULL;
-	uint32_t *dead_term = NULL, *dead_ord = NULL, *dead_list = NULL;
-	uint8_t *term_ok = NULL;
-	size_t n_new = 0, cap_new = 0, n_deadp = 0, cap_deadp = 0, n_dead = 0, cap_dead = 0;
-	uint64_t off, consumed_to, max_id;
-	nxsgpu_index_delta_t dl;
-	const uint32_t old_last_id = idx->last_id;
-	bool rebuild = false;
+	struct nxs_delta rd;
 	int ret = -1;
 
 	if (!idx->tmap || !idx->dmap) {
@@ -1018,7 +1244,7 @@ nxs_index_refresh(nxs_index_t *idx)
 		return 0;
 	}
 	if (idx->n_shards > 1) {
-		return 0;	/* a doc shard is a static snapshot (include/nxs.h) */
+		return 0;	/* a doc shard follows the files through nxs_docshard_refresh (include/nxs.h) */
 	}
 	if (idx->dev && nxsgpu_batches_in_flight(idx->dev) > 0) {
 		return 0;	/* the device arrays are in use: between batches only */
@@ -1030,181 +1256,147 @@ nxs_index_refresh(nxs_index_t *idx)
 	    TERMS_HDR_LEN + t_now > idx->tmap_len || DTMAP_HDR_LEN + d_now > idx->dmap_len) {
 		return refresh_rebuild(idx);	/* the files were replaced */
 	}
-	if (sync_terms(idx) == -1) {
+	if (sync_terms(idx, UINT64_MAX) == -1) {
 		nxs_clear_error(idx->nxs);
 		return refresh_rebuild(idx);
 	}
 
 	/* idx_dtmap_sync over the new blocks */
-	max_id = idx->n_ord ? idx->h_doc_ids[idx->n_ord - 1] : 0;
-	consumed_to = idx->dt_consumed;
-	for (off = idx->dt_consumed; off < d_now && !rebuild; ) {
-		const uint8_t *p = idx->dmap + DTMAP_HDR_LEN + off;
-		const uint64_t remaining = d_now - off;
-		uint64_t doc_id;
-		uint32_t doc_len, np;
-		bool ok = true;
-
-		if (remaining < 16) {
-			rebuild = true;
-			break;
-		}
-		doc_id = rd64(p);
-		doc_len = rd32(p + 8);
-		np = rd32(p + 12);
-		if ((uint64_t)np * 8 > remaining - 16) {
-			rebuild = true;
-			break;
-		}
-		if (doc_id == 0) {
-			/* deleted block: dtmap.c:364-367 */
-		} else if (doc_len == 0) {
-			/* tombstone (dtmap.c:374-381): drop the doc if it is loaded */
-			const int64_t o = ord_of(idx, doc_id);
-			bool pending = false;
-
-			for (size_t i = 0; i < n_new && !pending; i++) {
-				pending = nb_ids[i] == doc_id;
-			}
-			if (pending) {
-				rebuild = true;		/* added and removed within one delta */
-			} else if (o >= 0 && idx->h_alive[o]) {
-				const uint8_t *blk = idx->dmap + idx->h_blk_off[o];
-				const uint32_t n = idx->h_npairs[o];
-
-				if (n_dead == cap_dead) {
-					cap_dead = cap_dead ? cap_dead * 2 : 64;
-					dead_list = realloc(dead_list, cap_dead * sizeof(uint32_t));
-				}
-				dead_list[n_dead++] = (uint32_t)o;
-				idx->h_alive[o] = 2;	/* dying: committed below */
-				if (n_deadp + n > cap_deadp) {
-					cap_deadp = (n_deadp + n) * 2 + 64;
-					dead_term = realloc(dead_term, cap_deadp * sizeof(uint32_t));
-					dead_ord = realloc(dead_ord, cap_deadp * sizeof(uint32_t));
-				}
-				/* the removed doc's block still holds its pairs (only the doc
-				 * id was zeroed: dtmap.c:603) */
-				for (uint32_t j = 0; j < n; j++) {
-					dead_term[n_deadp] = rd32(blk + 16 + 8 * (size_t)j);
-					dead_ord[n_deadp] = (uint32_t)o;
-					n_deadp++;
-				}
-			}
-		} else {
-			const int64_t o = ord_of(idx, doc_id);
-
-			if (doc_id <= max_id || (o >= 0 && idx->h_alive[o])) {
-				rebuild = true;		/* out-of-order or re-used id */
-				break;
-			}
-			/* every pair must name a visible, live term: else stop here
-			 * (partial sync, dtmap.c:406-413,527-535) */
-			for (uint32_t j = 0; j < np && ok; j++) {
-				const uint32_t tid = rd32(p + 16 + 8 * (size_t)j);
-				ok = tid != 0 && tid <= idx->last_id && idx->terms[tid].tot_off != 0;
-			}
-			if (!ok) {
-				break;
-			}
-			if (n_new == cap_new) {
-				cap_new = cap_new ? cap_new * 2 : 64;
-				nb_off = realloc(nb_off, cap_new * sizeof(uint64_t));
-				nb_ids = realloc(nb_ids, cap_new * sizeof(uint64_t));
-				nb_base = realloc(nb_base, (cap_new + 1) * sizeof(uint64_t));
-			}
-			if (n_new == 0) {
-				if (!nb_base) {
-					nb_base = malloc(2 * sizeof(uint64_t));
-				}
-				nb_base[0] = 0;
-			}
-			nb_off[n_new] = DTMAP_HDR_LEN + off;
-			nb_ids[n_new] = doc_id;
-			nb_base[n_new + 1] = nb_base[n_new] + np;
-			n_new++;
-			max_id = doc_id;
-		}
-		off += 16 + (uint64_t)np * 8;
-		consumed_to = off;
-	}
-	if (rebuild || idx->n_ord + n_new >= UINT32_MAX - 1) {
-		for (size_t i = 0; i < n_dead; i++) {
-			idx->h_alive[dead_list[i]] = 1;
-		}
+	memset(&rd, 0, sizeof(rd));
+	rd.d_now = d_now;
+	rd.hd_docs = hd_docs;
+	rd.hd_tokens = hd_tokens;
+	if (delta_walk(idx, &rd, idx->n_ord ? idx->h_doc_ids[idx->n_ord - 1] : 0, true) != 0) {
+		delta_rollback(idx, &rd);
 		ret = refresh_rebuild(idx);
 		goto out;
 	}
-
-	term_ok = calloc((size_t)idx->last_id + 1, 1);
-	for (uint32_t id = 1; id <= idx->last_id; id++) {
-		term_ok[id] = idx->terms[id].tot_off != 0;
-	}
-	memset(&dl, 0, sizeof(dl));
-	dl.n_terms = idx->last_id;
-	dl.term_ok = term_ok;
-	dl.dtmap_img = idx->dmap;
-	dl.dtmap_len = DTMAP_HDR_LEN + d_now;
-	dl.blk_off = nb_off;
-	dl.doc_ids = nb_ids;
-	dl.pair_base = nb_base;
-	dl.n_new = n_new;
-	dl.dead_term = dead_term;
-	dl.dead_ord = dead_ord;
-	dl.n_dead_pairs = n_deadp;
-	dl.hdr_doc_count = (uint32_t)hd_docs;
-	dl.hdr_token_count = hd_tokens;
 	t_dbg[1] = dbg_ms();
-	if (nxsgpu_index_apply(idx->dev, &dl) != 0) {
-		for (size_t i = 0; i < n_dead; i++) {
-			idx->h_alive[dead_list[i]] = 1;
-		}
+	if (delta_apply(idx, &rd, false) != 0) {
+		delta_rollback(idx, &rd);
 		ret = refresh_rebuild(idx);
 		goto out;
 	}
 	t_dbg[2] = dbg_ms();
-	/* commit the host tables */
-	for (size_t i = 0; i < n_dead; i++) {
-		idx->h_alive[dead_list[i]] = 0;
-	}
-	if (idx->n_ord + n_new > idx->cap_ord) {
-		idx->cap_ord = (idx->n_ord + n_new) * 2 + 1024;
-		idx->h_doc_ids = realloc(idx->h_doc_ids, idx->cap_ord * sizeof(uint64_t));
-		idx->h_blk_off = realloc(idx->h_blk_off, idx->cap_ord * sizeof(uint64_t));
-		idx->h_npairs = realloc(idx->h_npairs, idx->cap_ord * sizeof(uint32_t));
-		idx->h_alive = realloc(idx->h_alive, idx->cap_ord);
-	}
-	for (size_t i = 0; i < n_new; i++) {
-		idx->h_doc_ids[idx->n_ord] = nb_ids[i];
-		idx->h_blk_off[idx->n_ord] = nb_off[i];
-		idx->h_npairs[idx->n_ord] = (uint32_t)(nb_base[i + 1] - nb_base[i]);
-		idx->h_alive[idx->n_ord] = 1;
-		idx->n_ord++;
-	}
-	idx->n_docs = idx->n_ord;
-	idx->dt_consumed = consumed_to;
-	idx->hdr_docs_seen = hd_docs;
-	idx->hdr_tokens_seen = hd_tokens;
-	/* term totals moved (dtmap.c:236,626): the "total > 0" flags of the BK image
-	 * and, with new terms, the image itself are brought up to date before the
-	 * next fuzzy search (nxs_index_bk_sync) */
-	idx->bk_flags_stale = true;
-	(void)old_last_id;
-	idx->n_incremental++;
+	delta_commit(idx, &rd);
 	ret = 0;
 	if (getenv("NXS_GPU_DEBUG_TIMING")) {
 		fprintf(stderr, "[nxs refresh] host walk %.1f ms, device apply %.1f ms, commit %.1f ms\n",
 		    t_dbg[1] - t_dbg[0], t_dbg[2] - t_dbg[1], dbg_ms() - t_dbg[2]);
 	}
 out:
-	free(nb_off);
-	free(nb_ids);
-	free(nb_base);
-	free(dead_term);
-	free(dead_ord);
-	free(dead_list);
-	free(term_ok);
+	delta_release(&rd);
 	return ret;
+}
+
+/* ---- N4: the doc-shard refresh's pieces (driven by nxs_docshard_refresh[_rank]) ---- */
+
+/*
+ * The snapshot one refresh consumes to.  nxsdtmap's length is read first: a
+ * block published before that read names terms published before it (the
+ * writer's order), so the nxsterms length read next covers them.
+ */
+void
+nxs_index_snapshot(const nxs_index_t *idx, nxs_snap_t *sn)
+{
+	sn->dtmap_len = be64toh(__atomic_load_n((const uint64_t *)(idx->dmap + 8), __ATOMIC_ACQUIRE));
+	sn->terms_len = be32toh(__atomic_load_n((const uint32_t *)(idx->tmap + 8), __ATOMIC_ACQUIRE));
+	sn->hdr_docs = rd32(idx->dmap + 24);
+	sn->hdr_tokens = rd64(idx->dmap + 16);
+}
+
+/*
+ * A shard's host walk to the agreed snapshot: the new terms into its dictionary,
+ * its share of the doc blocks validated and collected; no device state changes.
+ * 0: *out holds the delta (nxs_shard_merge / nxs_delta_abort); 1: only a full
+ * rebuild takes this snapshot; -1: error.
+ */
+int
+nxs_shard_walk(nxs_index_t *idx, const nxs_snap_t *sn, uint64_t max_id, bool take_new, nxs_delta_t **out)
+{
+	struct nxs_delta *rd;
+
+	*out = NULL;
+	if (idx->dev && nxsgpu_batches_in_flight(idx->dev) > 0) {
+		nxs_decl_err(idx->nxs, NXS_ERR_INVALID, "batches are in flight");
+		return -1;
+	}
+	if (remap_if_grown(idx) == -1) {
+		return 1;
+	}
+	if (sn->terms_len < idx->terms_consumed || sn->dtmap_len < idx->dt_consumed ||
+	    TERMS_HDR_LEN + sn->terms_len > idx->tmap_len || DTMAP_HDR_LEN + sn->dtmap_len > idx->dmap_len) {
+		return 1;	/* the files were replaced */
+	}
+	if (sync_terms(idx, sn->terms_len) == -1) {
+		nxs_clear_error(idx->nxs);
+		return 1;
+	}
+	if ((rd = calloc(1, sizeof(*rd))) == NULL) {
+		nxs_decl_err(idx->nxs, NXS_ERR_SYSTEM, "out of memory");
+		return -1;
+	}
+	rd->d_now = sn->dtmap_len;
+	rd->hd_docs = sn->hdr_docs;
+	rd->hd_tokens = sn->hdr_tokens;
+	if (delta_walk(idx, rd, max_id, take_new) != 0) {
+		nxs_delta_abort(idx, rd);
+		return 1;
+	}
+	*out = rd;
+	return 0;
+}
+
+void
+nxs_delta_abort(nxs_index_t *idx, nxs_delta_t *rd)
+{
+	if (rd) {
+		delta_rollback(idx, rd);
+		delta_release(rd);
+		free(rd);
+	}
+}
+
+/* the delta into the device CSR, impacts deferred (nxsgpu_index_set_global_df
+ * recomputes them once, with the collection-wide df); frees the delta; 0 / -1 */
+int
+nxs_shard_merge(nxs_index_t *idx, nxs_delta_t *rd)
+{
+	const double t0 = dbg_ms();
+	int ret = -1;
+
+	if (delta_apply(idx, rd, true) == 0) {
+		delta_commit(idx, rd);
+		rd->n_dead = 0;		/* committed: nothing to roll back */
+		ret = 0;
+		if (getenv("NXS_GPU_DEBUG_TIMING")) {
+			fprintf(stderr, "[nxs docshard refresh] shard %u: device merge %.1f ms, %zu appended, %zu removed\n",
+			    idx->shard, dbg_ms() - t0, rd->n_new, rd->n_deadp);
+		}
+	} else {
+		nxs_decl_err(idx->nxs, NXS_ERR_FATAL, "shard %u: device merge failed: %s", idx->shard, nxsgpu_last_error());
+	}
+	nxs_delta_abort(idx, rd);	/* (after a commit: nothing left to roll back) */
+	return ret;
+}
+
+/* a shard's full rebuild to the agreed snapshot: its slice by rank, as at open; 0 / -1 (old one kept) */
+int
+nxs_shard_rebuild(nxs_index_t *idx, const nxs_snap_t *sn)
+{
+	int r;
+
+	if (idx->dev && nxsgpu_batches_in_flight(idx->dev) > 0) {
+		nxs_decl_err(idx->nxs, NXS_ERR_INVALID, "batches are in flight");
+		return -1;
+	}
+	idx->pin = sn;
+	r = rebuild_snapshot(idx);
+	idx->pin = NULL;
+	if (r != 0 && idx->nxs->errcode == NXS_ERR_SUCCESS) {
+		nxs_decl_err(idx->nxs, NXS_ERR_FATAL, "shard %u: rebuild failed", idx->shard);
+	}
+	return r;
 }
 
 /*
