@@ -127,8 +127,9 @@ typedef struct {
 	/*
 	 * Per query CLASS (= one scan launch per batch): HIP events recorded on the stream
 	 * the class's kernels are launched on, around them.  cls_key = kind << 8 | shape << 4
-	 * bits | token bucket (nxs_gpu_search.hip: build_worklist); kind 1 k_scan1 / k_scan8,
-	 * 3 k_scanr, 4 k_scanm, 5 k_cold + k_scanm<.., DROP>, 6 k_scanb, 7 k_scanq, 0 k_scan.
+	 * bits | token bucket (nxs_gpu_int.h: cls_kind_t, cls_shape_t; nxs_gpu_plan.hip: classify_query); kind 1
+	 * k_scan1 / k_scan8, 3 k_scanr, 4 k_scanm, 5 k_cold + k_scanm<.., DROP>, 6 k_scanb, 7 k_scanq, 8 k_scans,
+	 * 9 k_cold + k_scans<.., DROP>, 0 k_scan.  Bit 7: a launch of the class's top doc ranges, sent ahead.
 	 */
 	uint32_t	n_cls;
 	uint32_t	cls_key[NXSGPU_PROF_CLS];

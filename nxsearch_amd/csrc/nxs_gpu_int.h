@@ -25,7 +25,9 @@
  *                         (heap.c:58-221; results.c:165-220) replayed exactly
  *  nxs_gpu_wide.hip       k_scanw: queries beyond the fixed-size plan
  *  nxs_gpu_fuzzy.hip      BK-tree search (bktree.c:219-275) + Levenshtein
- *  nxs_gpu_search.hip     work list, kernel dispatch, batches in flight
+ *  nxs_gpu_plan.hip       host only: query classes, the work list (build_worklist) and
+ *                         the layout of a batch's arrays (batch_layout)
+ *  nxs_gpu_search.hip     kernel dispatch, blocking search, batches in flight
  *  nxs_gpu_comm.hip       RCCL all-gather of the record blocks (query sharding)
  *
  * No MFMA anywhere: this is sparse gather/accumulate and byte/integer work,
@@ -103,7 +105,7 @@ struct dev_query_t {
 	uint32_t	outl_mask;	/* dropped tokens whose pbeg / pend name the term's OUTLIER list (the postings
 					 * above tcap, impact = the excess over it): scanned like a sparse term for the
 					 * bounds, never for the exact score (that comes from the column) */
-	uint32_t	outl_tfidf;	/* host only: the dropped tokens have outlier lists to put in place (build_worklist) */
+	uint32_t	outl_tfidf;	/* host only: the dropped tokens have outlier lists to put in place (classify_query) */
 	uint32_t	bm_col[8];	/* k_scanq: the token's block-presence bitmap (nxsgpu_index::d_blkmap row), ~0 = none */
 	uint32_t	qflags;		/* bit 0: no second chance on the accumulator tiles (pbeg / pend are not the
 					 * terms' lists) -- an overflowing range flags the query for the exact passes */
@@ -375,6 +377,19 @@ enum { MODE_TOPK = 0, MODE_COUNT = 1, MODE_ALL = 2, MODE_BIG = 3 };
 struct qmeta_t { uint32_t seg_first, n_groups, group_docs, pad; };
 struct item_t { uint32_t q, g; };
 
+/* scan_args_t::flags */
+enum : uint32_t {
+	SCAN_F_PRIO	= 1u << 0,	/* raise the wavefronts' issue priority (side-stream class) */
+	SCAN_F_RETRY	= 1u << 1,	/* k_scan8: the work items are the retry list's */
+	SCAN_F_DROP_B	= 1u << 3,	/* the sparse + dense class's second kernel is k_scanb<.., DROP> (NXS_GPU_DROPB,
+					 * up to five tokens) ... */
+	SCAN_F_DROP_S	= 1u << 4,	/* ... is k_scans<.., DROP> (wins over SCAN_F_DROP_B: nxs_launch_drop_class) */
+};
+/* replay_args_t::flags */
+enum : uint32_t {
+	REPLAY_F_ONE_LANE = 1u << 0,	/* 64 < k <= REPLAY_LDS_K on the one-lane kernel (NXS_GPU_OLDREPLAY) */
+};
+
 struct scan_args_t {
 	const posting_t *	post;
 	const dev_query_t *	queries;
@@ -393,9 +408,7 @@ struct scan_args_t {
 	float *			pub;		/* [segments] k-th best score of a finished range (0 = none) */
 	float *			pub_sk;		/* MODE_BIG: [segments][8] lower bounds of a finished range's ceil(k / 2^j)-th
 						 * best score, j = 0..5 (bigk_publish / bigk_hint) */
-	uint32_t		flags;		/* bit 0: raise the wavefronts' issue priority (side-stream class);
-						 * bit 1 (k_scan8): the work items are the retry list's;
-						 * bit 4: the sparse + dense class's second kernel is k_scans<.., DROP> */
+	uint32_t		flags;		/* SCAN_F_* */
 	/*
 	 * Ranges whose pending list overflowed on the mask path (k_scanm: a burst of docs
 	 * above a still-weak threshold -- it depends on when higher ranges publish theirs,
@@ -457,7 +470,7 @@ struct replay_args_t {
 	uint32_t *		log_cnt;
 	uint32_t		log_cap;
 	const uint32_t *	log_slot;	/* [Q] row of the log per query (NULL: q) */
-	uint32_t		flags;		/* bit 0: 64 < k <= REPLAY_LDS_K on the one-lane kernel (NXS_GPU_OLDREPLAY) */
+	uint32_t		flags;		/* REPLAY_F_* */
 };
 
 /* where the heap lives: global memory (any k), across the lanes (k <= 64), or in
@@ -467,8 +480,49 @@ struct replay_args_t {
 #define	HEAP_LDS	2
 #define	REPLAY_LDS_K	8000
 
-struct launch_t { uint32_t first, count, nt_bucket, kind, nomask, q_first, q_count; uint64_t postings; };	/* kind: 0 generic (9..32 tokens), 1 accumulator tiles / k_scan1, 3 k_scanr, 4 k_scanm, 5 k_cold + k_scanm<DROP>,
- * 6 k_scanb, 7 k_scanq, 8 k_scans, 9 k_cold + k_scans<DROP> */
+/*
+ * Query classes: which kernel(s) scan a query.  A class is (kind, shape, token-count bucket); a batch's
+ * queries are sorted by class and every class is one scan launch (launch_t).  The kinds' numbers are
+ * part of the profile's class key (include/nxs_gpu.h: kind << 8 | shape << 4 | bucket).
+ */
+enum cls_kind_t : uint32_t {
+	CLS_GENERIC	= 0,	/* k_scan: 9..32 tokens */
+	CLS_TILES	= 1,	/* accumulator tiles (k_scan8) / k_scan1 */
+	CLS_SCANR	= 3,	/* required terms: intersect first (k_scanr) */
+	CLS_SCANM	= 4,	/* mask path on register windows (k_scanm) */
+	CLS_DROP_M	= 5,	/* sparse + dense OR: k_cold + k_scanm<.., DROP> */
+	CLS_SCANB	= 6,	/* mask path on presence bits (k_scanb) */
+	CLS_SCANQ	= 7,	/* required terms through the block-presence bitmaps (k_scanq) */
+	CLS_SCANS	= 8,	/* mask path on doc stripes (k_scans) */
+	CLS_DROP_S	= 9,	/* sparse + dense OR: k_cold + k_scans<.., DROP> */
+	CLS_KINDS	= 10
+};
+enum cls_shape_t : uint32_t {
+	SHAPE_MASK	= 0,	/* the truth table as a mask array */
+	SHAPE_OR	= 1,	/* pure OR: every non-empty presence mask matches (k_scanr: rounds over an LDS hash table) */
+	SHAPE_AND2	= 2	/* two-token AND */
+};
+/* the sparse + dense class: its own stream, top ranges sent ahead */
+static inline bool cls_sparse_dense(uint32_t kind) { return kind == CLS_DROP_M || kind == CLS_DROP_S; }
+/* the conjunctive classes: run early, on the upload stream */
+static inline bool cls_conjunctive(uint32_t kind) { return kind == CLS_SCANR || kind == CLS_SCANQ; }
+/* the mask path: top-k filter pass only, the exact passes take the accumulator tiles */
+static inline bool cls_mask_path(uint32_t kind) { return kind == CLS_SCANM || kind == CLS_SCANB || kind == CLS_SCANS; }
+/* classes whose overflowed ranges get a second chance on the tiles (scan_args_t::retry_items) */
+static inline bool cls_has_retry(uint32_t kind) { return cls_mask_path(kind) || cls_sparse_dense(kind); }
+
+struct qclass_t {
+	uint32_t	kind, shape, bucket;	/* cls_kind_t, cls_shape_t, nt_bucket */
+	bool operator==(const qclass_t &o) const { return kind == o.kind && shape == o.shape && bucket == o.bucket; }
+	bool operator!=(const qclass_t &o) const { return !(*this == o); }
+	/* index into a table of CLS_SLOTS counters */
+	uint32_t slot() const { return (kind * 4 + shape) * 16 + bucket; }
+};
+#define	CLS_SLOTS	(CLS_KINDS * 4 * 16)
+
+/* one scan launch: the items [first, first + count) of a class, whose queries are qorder[q_first ...
+ * + q_count) (q_count == 0: top levels sent ahead -- no query ends in it, no replay behind it) */
+struct launch_t { uint32_t first, count, nt_bucket, kind /* cls_kind_t */, nomask /* cls_shape_t */, q_first, q_count; uint64_t postings; };
 
 struct worklist_t {
 	std::vector<qmeta_t>	qmeta;
@@ -491,7 +545,7 @@ carve(uint8_t *&p, size_t n)
 }
 
 /* k_scanr: queries with >= 4 required terms take rounds of whole driver windows
- * over an LDS hash table (a class of their own: build_worklist) */
+ * over an LDS hash table (a class of their own: classify_query) */
 #ifndef SCANR_HASH
 #define	SCANR_HASH	1		/* a round = a whole driver window, its docs in an LDS hash table */
 #endif
@@ -516,8 +570,62 @@ void	pick_record_stream(nxsgpu_index_t *ix);
 void	bk_aux_free(nxsgpu_index_t *ix);
 int	bk_aux_build(nxsgpu_index_t *ix, const nxsgpu_bknode_t *nodes, uint32_t n);
 
-/* ---- nxs_gpu_search.hip ---- */
+/* ---- nxs_gpu_plan.hip ---- */
 void	delete_worklist(worklist_t *);
+/* classes, ranges, items and launches of a batch; rewrites hq[i] where a TF-IDF query's dropped tokens
+ * are scanned through their outlier lists.  solo: nothing else in flight; big_k: the limit if > 64 */
+void	build_worklist(const nxsgpu_index_t *ix, dev_query_t *hq, uint32_t nq, worklist_t &wl, bool solo, uint32_t big_k);
+
+/*
+ * The arrays of one batch.  The SAME layout is carved from the pinned staging area and from the device
+ * workspace, so the uploaded block [0, up_len) and the block that comes back [ovf, ovf + down_len) are one
+ * copy each, at equal offsets on both sides; [0, host_len) is what the host side needs at all.
+ */
+struct batch_dims_t {
+	uint32_t	nq;
+	uint64_t	nseg;
+	uint32_t	seg_cap, k;
+	bool		big;		/* limit > 64: pub_sk */
+	/* optional parts (0 / false: none, the member has size 0) */
+	bool		rec_slots;	/* record mode: rec_slot [nq] */
+	uint32_t	status_words;	/* record mode: the block's status words, staged on the host */
+	bool		results;	/* out_ids / out_sc [nq][k], out_cnt [nq] */
+	uint32_t	log_cap;	/* candidate log (doc-sharded mode): log_* [nq][log_cap] */
+};
+struct batch_layout_t {
+	/* host -> device, one copy */
+	dev_query_t *	q;		/* [nq] (first: its place does not depend on nseg) */
+	qmeta_t *	qmeta;		/* [nq] */
+	item_t *	items;		/* [nseg] */
+	uint32_t *	bnd_q;		/* [nseg + nq] */
+	uint32_t *	qorder;		/* [nq] */
+	uint32_t *	rec_slot;	/* [nq] */
+	float *		pub;		/* [nseg], zeroed */
+	uint32_t *	retry_cnt;	/* [RETRY_LISTS], zeroed */
+	uint32_t *	ovf;		/* [nq], zeroed -- and the first array of what comes back */
+	size_t		up_len;
+	uint64_t *	out_ids;
+	float *		out_sc;
+	uint32_t *	out_cnt;
+	size_t		down_len;	/* from ovf on */
+	uint32_t *	status;
+	size_t		host_len;
+	/* what only the kernels touch */
+	uint32_t *	seg_count;	/* [nseg] */
+	uint32_t *	cursors;	/* [nseg + nq][MAX_TOKENS] */
+	uint32_t *	cand_doc;	/* [nseg][seg_cap] */
+	float *		cand_sc;
+	uint32_t *	cold_state;	/* [nseg][16] */
+	float *		cold_top;	/* [nseg][64] */
+	item_t *	retry_items;	/* [RETRY_LISTS][RETRY_CAP] */
+	float *		pub_sk;		/* [nseg][8] */
+	uint64_t *	log_ids;
+	float *		log_sc;
+	uint32_t *	log_cnt, *log_slot;	/* [nq] */
+	size_t		len;
+};
+/* base == NULL: offsets and sizes only */
+batch_layout_t	batch_layout(uint8_t *base, const batch_dims_t &d);
 
 /* ---- nxs_gpu_comm.hip ---- */
 int	comm_allgather_dev(nxsgpu_comm_t *, const void *send, void *recv, size_t bytes, hipStream_t);
@@ -533,7 +641,7 @@ void	nxs_launch_scanm(uint32_t nt_bucket, bool gen, unsigned grid, hipStream_t s
 void	nxs_launch_drop_class(uint32_t nt_bucket, unsigned grid, hipStream_t st, const scan_args_t &a);
 /* the mask path on doc stripes (k_scans: rank directories instead of per-term register windows) */
 void	nxs_launch_scans(uint32_t nt_bucket, bool gen, unsigned grid, hipStream_t st, const scan_args_t &a);
-/* ... the sparse + dense class's second kernel on stripes (k_scans<.., DROP>; scan_args_t::flags bit 4 makes
+/* ... the sparse + dense class's second kernel on stripes (k_scans<.., DROP>; SCAN_F_DROP_S makes
  * nxs_launch_drop_class launch it behind k_cold) */
 void	nxs_launch_scans_drop(uint32_t nt_bucket, unsigned grid, hipStream_t st, const scan_args_t &a);
 /* the mask path on presence bits, candidates scored one per lane (k_scanb) */

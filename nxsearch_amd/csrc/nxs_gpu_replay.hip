@@ -1070,7 +1070,7 @@ nxs_launch_replay(int heap, unsigned grid, size_t dyn_lds, hipStream_t st, const
 	switch (heap) {
 	case HEAP_REG: hipLaunchKernelGGL(k_replay<HEAP_REG>, dim3(grid), dim3(WAVE), 0, st, r); break;
 	case HEAP_LDS:
-		if (r.flags & 1) {	/* NXS_GPU_OLDREPLAY: the one-lane form, for A/B runs */
+		if (r.flags & REPLAY_F_ONE_LANE) {	/* NXS_GPU_OLDREPLAY: the one-lane form, for A/B runs */
 			hipLaunchKernelGGL(k_replay<HEAP_LDS>, dim3(grid), dim3(WAVE), dyn_lds, st, r);
 		} else {
 			hipLaunchKernelGGL(k_replay_coop, dim3(grid), dim3(WAVE), dyn_lds, st, r);

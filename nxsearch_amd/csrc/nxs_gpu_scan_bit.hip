@@ -111,7 +111,7 @@ k_scanb(const scan_args_t A)
 	const unsigned long long clk0 = STAT_CLK();
 	(void)clk0;
 	if constexpr (DROP) {
-		if (A.flags & 1) {
+		if (A.flags & SCAN_F_PRIO) {
 			__builtin_amdgcn_s_setprio(3);
 		}
 	}

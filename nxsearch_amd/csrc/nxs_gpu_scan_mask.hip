@@ -134,7 +134,7 @@ k_scanm(const scan_args_t A)
 	if constexpr (DROP) {
 		/* few, latency-bound wavefronts beside the throughput-bound classes on
 		 * the other stream: let the CU's arbiter prefer them */
-		if (A.flags & 1) {
+		if (A.flags & SCAN_F_PRIO) {
 			__builtin_amdgcn_s_setprio(3);
 		}
 	}
@@ -1012,19 +1012,19 @@ nxs_launch_drop_class(uint32_t nt_bucket, unsigned grid_, hipStream_t st, const 
 	case 2:
 	case 3:
 		hipLaunchKernelGGL((k_cold<3, false>), grid, block, 0, st, a);
-		if (a.flags & 16) { nxs_launch_scans_drop(nt_bucket, grid_, st, a); break; }
-		if (a.flags & 8) { nxs_launch_scanb(nt_bucket, false, true, grid_, st, a); break; }
+		if (a.flags & SCAN_F_DROP_S) { nxs_launch_scans_drop(nt_bucket, grid_, st, a); break; }
+		if (a.flags & SCAN_F_DROP_B) { nxs_launch_scanb(nt_bucket, false, true, grid_, st, a); break; }
 		hipLaunchKernelGGL((k_scanm<3, false, true>), grid, block, 0, st, a);
 		break;
 	case 5:
 		hipLaunchKernelGGL((k_cold<5, false>), grid, block, 0, st, a);
-		if (a.flags & 16) { nxs_launch_scans_drop(nt_bucket, grid_, st, a); break; }
-		if (a.flags & 8) { nxs_launch_scanb(nt_bucket, false, true, grid_, st, a); break; }
+		if (a.flags & SCAN_F_DROP_S) { nxs_launch_scans_drop(nt_bucket, grid_, st, a); break; }
+		if (a.flags & SCAN_F_DROP_B) { nxs_launch_scanb(nt_bucket, false, true, grid_, st, a); break; }
 		hipLaunchKernelGGL((k_scanm<5, false, true>), grid, block, 0, st, a);
 		break;
 	default:
 		hipLaunchKernelGGL((k_cold<8, false>), grid, block, 0, st, a);
-		if (a.flags & 16) { nxs_launch_scans_drop(nt_bucket, grid_, st, a); break; }
+		if (a.flags & SCAN_F_DROP_S) { nxs_launch_scans_drop(nt_bucket, grid_, st, a); break; }
 		hipLaunchKernelGGL((k_scanm<8, false, true>), grid, block, 0, st, a);
 		break;
 	}

@@ -331,7 +331,7 @@ k_scan8(const scan_args_t A)
 
 	const unsigned lane = threadIdx.x;
 	item_t item;
-	if (A.flags & 2) {
+	if (A.flags & SCAN_F_RETRY) {
 		/* second chance of the ranges that overflowed on the mask path */
 		if (blockIdx.x >= min(*A.retry_count, A.retry_cap)) {
 			return;

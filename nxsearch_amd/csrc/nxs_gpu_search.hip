@@ -1,443 +1,8 @@
 /*
- * nxs_gpu_search.hip -- work list, kernel dispatch, blocking search (exact two-pass path), pipelined batches, shard slices
+ * nxs_gpu_search.hip -- kernel dispatch, blocking search (exact two-pass path), pipelined batches, shard slices
  * (MI355X / gfx950 query path of nxsearch; see nxs_gpu_int.h for the map of the files)
  */
 #include "nxs_gpu_int.h"
-
-/* ---- search --------------------------------------------------------- */
-
-/*
- * Work decomposition: every query's doc space is cut into n_groups equal
- * ranges (multiples of TILE_W), one wavefront each.  The number of ranges is
- * proportional to the query's share of the batch's postings, so a query with
- * long lists gets many wavefronts and a sparse one a single one (whose fixed
- * costs -- cursor searches, warm-up of the candidate threshold -- are then
- * paid once).  Items are grouped by kernel class (token-count bucket x
- * tile/step path) and emitted heaviest query first inside a class.
- */
-
-void
-delete_worklist(worklist_t *wl)
-{
-	delete wl;
-}
-
-static uint32_t
-nt_bucket(uint32_t nt)
-{
-	return nt <= 1 ? 1 : nt <= 2 ? 2 : nt <= 3 ? 3 : nt <= 5 ? 5 : 8;
-}
-
-static void
-build_worklist(const nxsgpu_index_t *ix, dev_query_t *hq, uint32_t nq, worklist_t &wl, bool solo = false,
-    uint32_t big_k = 0)
-{
-	const uint64_t tiles = std::max<uint64_t>(1, (ix->n_docs + TILE_W - 1) / TILE_W);
-	const gpu_cfg_t &cf = ix->cfg;
-	/* (a batch that has the GPU to itself is latency-bound: shorter ranges, more of them) */
-	const uint64_t target = cf.wave_target, min_post = solo ? std::min(cf.min_post, cf.min_post_solo) : cf.min_post;
-	const bool use_scanr = cf.use_scanr && ix->n_docs < (1ull << 31);
-	const bool mask_off = cf.mask_off;
-	const uint32_t rmin = cf.rmin;	/* 3: "a AND b" takes k_scan8's sign-bit path */
-	const bool by_level = cf.by_level;
-	/* (limits > 64 -- big_k -- filter on a histogram threshold: the accumulator tiles,
-	 * k_scanr and k_scan1 have that mode, the mask path and the dense-term class do not) */
-	/* NXS_GPU_NOSTRAGGLER: keep tiny tile-path classes (below) as launches of their own */
-	const bool merge_stragglers = !cf.no_straggler;
-	const bool use_scanm = cf.use_scanm && ix->n_docs < (1ull << 31) && big_k == 0;
-	const bool scanm_general = cf.scanm_general;
-	const uint32_t scanm_minnt = cf.scanm_minnt, scanm_maxnt = cf.scanm_maxnt;
-	/* k_scanm if the densest list holds at most this fraction of the docs */
-	const double scanm_dens = cf.scanm_dens;
-	std::vector<uint64_t> work(nq);
-	std::vector<uint32_t> order(nq), cls(nq);
-	uint64_t total = 0;
-
-	for (uint32_t i = 0; i < nq; i++) {
-		uint64_t w = 0, wmax = 0;
-		for (uint32_t t = 0; t < hq[i].nt; t++) {
-			const uint64_t df = hq[i].pend[t] - hq[i].pbeg[t];
-			w += df;
-			wmax = std::max(wmax, df);
-		}
-		work[i] = w;
-		total += w;
-		order[i] = i;
-		if (hq[i].nt > 8) {
-			cls[i] = 0;
-		} else {
-			/* pure OR: every non-empty presence mask matches => no mask array */
-			bool or_only = hq[i].nt >= 2 && mask_off;
-			for (uint32_t m = 1; or_only && m < (1u << hq[i].nt); m++) {
-				or_only = (hq[i].truth[m >> 5] >> (m & 31)) & 1;
-			}
-			const uint32_t mm = or_only ? 1u : 0u;
-			cls[i] = 1u * 64 + mm * 16 + nt_bucket(hq[i].nt);
-			/* pure OR of 2..8 tokens whose lists are sparse: mask path (k_scanm).
-			 * Dense lists stream faster through the accumulator tiles. */
-			/* ... or any expression without a required token: the bound in the
-			 * byte map does not depend on the operators, the truth table is
-			 * applied to the few docs that get scored
-			 * (only where matches are common enough for a threshold to form:
-			 * at least half of the tokens satisfy the expression on their own --
-			 * "(a AND b) OR (c AND d)" floods the scoring stage and stays on the
-			 * accumulator tiles: 3.3 ms there, 5.4 ms here) */
-			uint32_t singles = 0;
-			for (uint32_t t = 0; t < hq[i].nt && t < 8; t++) {
-				const uint32_t m1 = 1u << t;
-				singles += (hq[i].truth[m1 >> 5] >> (m1 & 31)) & 1;
-			}
-			const bool no_req = hq[i].req == 0 && hq[i].nt >= 2 && hq[i].nt <= 8 && mm != 2 &&
-			    2 * singles >= hq[i].nt;
-			if ((or_only || (no_req && scanm_general)) && use_scanm &&
-			    hq[i].nt >= scanm_minnt && hq[i].nt <= scanm_maxnt &&
-			    (double)wmax <= scanm_dens * (double)ix->n_docs) {
-				cls[i] = 4u * 64 + (or_only ? 16u : 0u) + nt_bucket(hq[i].nt);
-				/* ... on presence bits (k_scanb) where that kernel is the faster one: its cost per
-				 * posting does not fall with the lists' density as the byte map's does, so it
-				 * takes the queries whose lists TOGETHER hold few docs (measured cross-over on
-				 * 10M docs: 5-term ORs of rank 500-1000 -29 %, of rank 100-1000 +9 %) */
-				if (cf.use_scanb && hq[i].nt <= 5 && (double)w <= cf.scanb_dens * (double)ix->n_docs) {
-					cls[i] += 2u * 64;
-				}
-				/* ... on doc stripes (k_scans) when every term has a rank directory: the stripes'
-				 * slices of the lists are table lookups, no per-term window state */
-				if ((cls[i] >> 6) == 4 && cf.use_scans && ix->n_post < (1ull << 32) && ix->d_bmrank) {
-					bool all = true;
-					for (uint32_t t = 0; t < hq[i].nt; t++) {
-						all = all && hq[i].bm_col[t] != 0xffffffffu;
-					}
-					if (all) {
-						cls[i] += 4u * 64;
-						/* (longer ranges: a stripe range's fixed costs -- set-up, the cold sub-ranges, ~1.3 flushes --
-						 * are paid per wavefront) */
-						if (cf.scans_workpct != 100) {
-							total -= work[i];
-							work[i] = std::max<uint64_t>(1, work[i] * cf.scans_workpct / 100);
-							total += work[i];
-						}
-					}
-				}
-			} else if (or_only && use_scanm && cf.use_drop && hq[i].drop_mask &&
-			    hq[i].nt >= scanm_minnt && hq[i].nt <= scanm_maxnt) {
-				/*
-				 * A pure OR of sparse terms AND dense ones: the mask path on the
-				 * sparse terms, the dense lists leave the scan once the threshold
-				 * exceeds their joint ceiling (k_scanm<.., DROP>).  Needs enough
-				 * sparse postings for a threshold to form in every doc range; the
-				 * work is what the sparse lists hold.
-				 */
-				uint64_t ws = 0;
-				uint32_t n_sparse = 0;
-				for (uint32_t t = 0; t < hq[i].nt; t++) {
-					if (!((hq[i].drop_mask >> t) & 1)) {
-						ws += hq[i].pend[t] - hq[i].pbeg[t];
-						n_sparse++;
-					} else if (hq[i].outl_tfidf) {
-						const size_t c = hq[i].drop_col[t];
-						ws += ix->outl_off[c + 1] - ix->outl_off[c];	/* (a dropped term's outlier list is scanned) */
-					}
-				}
-				if (n_sparse && ws >= cf.drop_minpost) {
-					/* TF-IDF: from here on the dropped tokens' lists are their outlier lists
-					 * (kernels that stream the terms' own lists must not see this query again:
-					 * qflags) */
-					for (uint32_t t = 0; t < hq[i].nt && hq[i].outl_tfidf && !cf.drop_tiles; t++) {
-						const size_t c = hq[i].drop_col[t];
-						if (((hq[i].drop_mask >> t) & 1) && ix->outl_off[c + 1] > ix->outl_off[c]) {
-							hq[i].pbeg[t] = ix->outl_off[c];
-							hq[i].pend[t] = ix->outl_off[c + 1];
-							hq[i].outl_mask |= 1u << t;
-							hq[i].qflags |= 1;
-						}
-					}
-					if (!cf.drop_tiles) {
-						total -= work[i];
-						work[i] = cf.drop_workmul * (ws + 16384);	/* latency-bound wavefronts: more, shorter ranges */
-						total += work[i];
-					}
-					cls[i] = 5u * 64 + 16u + nt_bucket(hq[i].nt);
-					/* ... on doc stripes (k_cold + k_scans<.., DROP>) if the sparse terms all have a rank
-					 * directory and no dropped term brings an outlier list (those have none) */
-					if (cf.use_scans && cf.use_scans_drop && !hq[i].outl_tfidf && ix->d_dense_q8 && ix->n_post < (1ull << 32) && ix->d_bmrank && !hq[i].outl_mask) {
-						bool all = true;
-						for (uint32_t t = 0; t < hq[i].nt; t++) {
-							all = all && (((hq[i].drop_mask >> t) & 1) || hq[i].bm_col[t] != 0xffffffffu);
-						}
-						if (all) {
-							cls[i] = 9u * 64 + 16u + nt_bucket(hq[i].nt);
-						}
-					}
-				}
-			}
-			/* required terms: intersect first (k_scanr).  Its work is set by
-			 * the shortest required list; longer lists are mostly skipped */
-			if (hq[i].n_req && hq[i].nt >= rmin && use_scanr) {
-				const uint64_t dfd = hq[i].pend[hq[i].slot_tok[0]] - hq[i].pbeg[hq[i].slot_tok[0]];
-				uint64_t wr = 0;
-				for (uint32_t t = 0; t < hq[i].nt; t++) {
-					wr += std::min<uint64_t>(hq[i].pend[t] - hq[i].pbeg[t], 4 * dfd);
-				}
-				total -= work[i];
-				work[i] = wr;
-				total += wr;
-				/* (four required terms and more: rounds of whole driver windows, k_scanr<.., true>) */
-			cls[i] = 3u * 64 + ((SCANR_HASH && hq[i].n_req >= 4) ? 16u : 0u) + nt_bucket(hq[i].nt);
-				/*
-				 * Two required terms and more that all have a block-presence bitmap: AND the
-				 * bitmaps and look at the postings of the surviving 64-doc blocks only
-				 * (k_scanq) -- if few blocks are expected to survive (independent lists: a
-				 * block holds term t with probability 1 - (1 - df_t / N)^64) against what
-				 * the driver list would cost k_scanr.
-				 */
-				if (cf.use_blkmap && hq[i].n_req >= 2 && ix->n_post < (1ull << 32)) {
-					double surv = (double)ix->n_docs / 64.0;
-					double em = (double)ix->n_docs;		/* expected docs holding every required term */
-					bool all = true;
-					for (uint32_t t = 0; t < hq[i].nt; t++) {
-						if (!((hq[i].req >> t) & 1)) {
-							continue;
-						}
-						all = all && hq[i].bm_col[t] != 0xffffffffu;
-						const double rho = (double)(hq[i].pend[t] - hq[i].pbeg[t]) / (double)std::max<uint64_t>(ix->n_docs, 1);
-						double e64 = 1.0 - std::min(rho, 1.0);	/* ^64 by squaring (std::pow: 2 500 calls a batch) */
-						e64 *= e64; e64 *= e64; e64 *= e64; e64 *= e64; e64 *= e64; e64 *= e64;
-						surv *= 1.0 - e64;
-						em *= std::min(rho, 1.0);
-					}
-					/* (limits > 64: k_scanq<.., BIG> emits EVERY match -- for queries that expect a
-					 * handful; more than a range's candidate list holds sends the query to the exact path) */
-					if (all && surv * cf.bm_gain < (double)dfd && (big_k == 0 || em < cf.bigq_em)) {
-						total -= work[i];
-						/* the bitmaps' words + the surviving blocks (a lane each), in posting units */
-						work[i] = (uint64_t)(ix->n_docs / 256 + surv * 64.0) + 1;
-						total += work[i];
-						cls[i] = 7u * 64 + (cls[i] & 16u) + nt_bucket(hq[i].nt);
-					}
-				}
-			}
-		}
-	}
-	/*
-	 * Stragglers.  A pure-OR query whose lists are too dense for the mask path and that
-	 * cannot drop them either (two dense terms, a ceiling too close to the sparse ones)
-	 * takes the accumulator tiles -- a class of ONE or two queries in a C3 batch: a launch
-	 * of its own on the scan stream, 0.1 ms of latency for 8 MB of postings, with nothing
-	 * to run beside.  The mask kernel takes any density (it is merely slower per dense
-	 * posting): up to four such queries join the batch's mask-path class of their shape,
-	 * where their ranges are wavefronts among tens of thousands.
-	 */
-	if (merge_stragglers && use_scanm) {
-		uint32_t n_in[16 * 64] = { 0 };
-		for (uint32_t i = 0; i < nq; i++) {
-			n_in[cls[i] & 1023]++;
-		}
-		/* (the batch's mask-path class of a shape: on doc stripes -- k_scans -- if the query's terms all have
-		 * a rank directory and that class is the populated one, else on register windows) */
-		auto mask_class = [&](uint32_t i, uint32_t shape) -> uint32_t {
-			bool all = cf.use_scans && ix->n_post < (1ull << 32) && ix->d_bmrank;
-			for (uint32_t t = 0; all && t < hq[i].nt; t++) {
-				all = hq[i].bm_col[t] != 0xffffffffu;
-			}
-			return (all && n_in[8u * 64 + shape] >= 32) ? 8u * 64 + shape : 4u * 64 + shape;
-		};
-		for (uint32_t i = 0; i < nq; i++) {
-			const uint32_t c = cls[i];
-			if ((c >> 6) == 1 && ((c >> 4) & 3) == 1 && (c & 15) >= 2 && n_in[c] <= 4 &&
-			    hq[i].nt >= scanm_minnt && hq[i].nt <= scanm_maxnt) {
-				const uint32_t to = mask_class(i, 16u + (c & 15));
-				if (n_in[to] >= 32) {
-					cls[i] = to;
-				}
-			}
-			/* (the same for a handful of very sparse queries that would take k_scanb: a launch of
-			 * their own only pays with enough of them) */
-			if ((c >> 6) == 6 && n_in[c] < 64) {
-				const uint32_t to = mask_class(i, c & 63);
-				if (n_in[to] >= 32) {
-					cls[i] = to;
-				}
-			}
-		}
-	}
-	/* (limits > 64: a range's own threshold needs well over k matches to form, and
-	 * every range that starts cold emits k candidates before it has one) */
-	/* (a batch with the stripe class: somewhat longer ranges for everything -- measured on C3, 57 344 against 65 536
-	 * wavefronts with the class itself at 70 %: 1.00 -> 1.05 M queries/s; single-token batches keep the finer split) */
-	bool any_scans = false;
-	for (uint32_t i = 0; i < nq && !any_scans; i++) {
-		any_scans = (cls[i] >> 6) == 8;
-	}
-	/* (... and a huge batch -- C5: 29 G postings -- more wavefronts than the target: a range of more than cf.max_post
-	 * postings leaves the step's tail to a few long wavefronts (C5: 358k -> 377k queries/s); at most four times the target: the staging area's bound) */
-	uint64_t target_eff = any_scans ? cf.wave_target_scans : target;
-	target_eff = std::min<uint64_t>(4 * target_eff, std::max<uint64_t>(target_eff, total / std::max<uint64_t>(cf.max_post, 1)));
-	const uint64_t per_wave = std::max<uint64_t>(std::max<uint64_t>(min_post, (uint64_t)big_k * cf.big_minpost),
-	    total / std::max<uint64_t>(target_eff, 1) + 1);
-	/* launch order of the classes: the mask path first -- a class's heap replay
-	 * runs beside the NEXT class's scan, and the last class (required-term
-	 * queries: few candidates, short replay) is the one left exposed */
-	/* (the sparse + dense class leads: it runs on a stream of its own, beside the rest) */
-	auto cls_key = [&](uint32_t c) -> uint32_t { return (c >> 6) == 9 ? (c & 63) : (c >> 6) == 5 ? 32 + (c & 63) : (c >> 6) == 8 ? 64 + (c & 63) : (c >> 6) == 4 ? 128 + (c & 63) : (c >> 6) == 6 ? 192 + (c & 63) : c + 256; };
-	std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
-		if (cls[x] != cls[y]) return cls_key(cls[x]) < cls_key(cls[y]);
-		return work[x] != work[y] ? work[x] > work[y] : x < y;
-	});
-	wl.qmeta.assign(nq, qmeta_t());
-	wl.items.clear();
-	wl.launches.clear();
-	wl.n_segs = 0;
-	wl.need_cursors = false;
-	for (uint32_t i = 0; i < nq; i++) {
-		uint64_t per_i = per_wave;
-		if (solo) {
-			/*
-			 * Alone on the GPU every range starts cold and emits its own early
-			 * maxima (~10 (1 + ln(postings / 10)) candidates each), which the replay
-			 * then streams through one wavefront; a range's scan is a chain of
-			 * dependent window loads.  Scan time falls with the number of ranges R,
-			 * replay time grows with it: the sum is smallest near R = sqrt(n / 84),
-			 * i.e. sqrt(84 n) postings per range (2M postings: 154 ranges, not 2000).
-			 */
-			/* (never finer than the batch-wide rule: the work list's size bound rests on it) */
-			per_i = std::max<uint64_t>(per_wave, (uint64_t)std::sqrt(84.0 * (double)work[i]));
-		}
-		uint64_t g = std::max<uint64_t>(1, (work[i] + per_i - 1) / per_i);
-		g = std::min<uint64_t>(g, tiles);
-		g = std::min<uint64_t>(g, 65535);
-		const uint64_t tiles_per = (tiles + g - 1) / g;
-		g = (tiles + tiles_per - 1) / tiles_per;
-		qmeta_t &m = wl.qmeta[i];
-		m.n_groups = (uint32_t)g;
-		m.group_docs = (uint32_t)std::min<uint64_t>(tiles_per * TILE_W, 0xffffffffu & ~(uint64_t)(TILE_W - 1));
-		/* single-token queries on k_scan1: any split of the list into contiguous
-		 * pieces, highest docs first, feeds the heap the same sequence -- split by
-		 * posting index and the batch needs no k_cursors launch */
-		m.pad = ((cls[i] >> 6) == 1 && (cls[i] & 15) == 1 && !cf.no_scan1 && !cf.old_scan &&
-		    ix->n_docs < (1ull << 31)) ? 1u : 0u;
-		wl.need_cursors = wl.need_cursors || m.pad == 0;
-	}
-	for (uint32_t i = 0; i < nq; i++) {
-		wl.qmeta[i].seg_first = wl.n_segs;
-		wl.n_segs += wl.qmeta[i].n_groups;
-	}
-	/* (both arrays are sized once and written through plain pointers: 130 000 push_back calls cost 0.1 ms a batch) */
-	wl.bnd_q.resize((size_t)wl.n_segs + nq);
-	{
-		uint32_t *bp = wl.bnd_q.data();
-		for (uint32_t i = 0; i < nq; i++) {
-			/* query i owns boundaries seg_first + i ... + n_groups (inclusive) */
-			bp = std::fill_n(bp, (size_t)wl.qmeta[i].n_groups + 1, i);
-		}
-	}
-	wl.items.resize(wl.n_segs);
-	item_t *const items = wl.items.data();
-	size_t n_items = 0;
-	wl.qorder = order;
-	/*
-	 * Inside a class, items go out level by level: level l of every query
-	 * (its l-th highest doc range) before level l+1 of any.  All items carry
-	 * about per_wave postings, so this costs no balance, and it spreads one
-	 * query's ranges in time: when a range starts, higher ranges of its query
-	 * have usually finished and published their threshold (range_hint).
-	 */
-	for (uint32_t o0 = 0; o0 < nq; ) {
-		uint32_t o1 = o0, max_g = 0;
-		while (o1 < nq && cls[order[o1]] == cls[order[o0]]) {
-			max_g = std::max(max_g, wl.qmeta[order[o1]].n_groups);
-			o1++;
-		}
-		launch_t l;
-		l.postings = 0;
-		l.first = (uint32_t)n_items;
-		l.nt_bucket = cls[order[o0]] & 15;
-		l.nomask = (cls[order[o0]] >> 4) & 3;	/* 0 mask array, 1 pure OR, 2 two-token AND */
-		l.kind = cls[order[o0]] >> 6;
-		if (by_level) {
-			/* the class is sorted by work, so n_groups does not increase along
-			 * it (checked): the queries that still have a level `lev` form a
-			 * prefix, and the loop is linear in the number of items */
-			bool mono = true;
-			for (uint32_t oi = o0 + 1; oi < o1 && mono; oi++) {
-				mono = wl.qmeta[order[oi]].n_groups <= wl.qmeta[order[oi - 1]].n_groups;
-			}
-			uint32_t live_end = o1;
-			for (uint32_t lev = 0; lev < max_g; lev++) {
-				while (mono && live_end > o0 && wl.qmeta[order[live_end - 1]].n_groups <= lev) {
-					live_end--;
-				}
-				for (uint32_t oi = o0; oi < live_end; oi++) {
-					const uint32_t i = order[oi];
-					if (lev < wl.qmeta[i].n_groups) {
-						item_t it;
-						it.q = i;
-						it.g = wl.qmeta[i].n_groups - 1 - lev;
-						items[n_items++] = it;
-					}
-				}
-				/*
-				 * Single-token queries (k_scan1: a wavefront is ~20 us of streaming):
-				 * a dense term is thousands of ranges that would all start at once,
-				 * cold, each handing its ~10 (1 + ln(postings / 10)) early maxima to
-				 * the one wavefront that replays the query -- 150 000 candidates for a
-				 * term holding 90 % of 10M docs, 0.3 ms of replay behind 0.05 ms of
-				 * scanning.  The TOP range of every query goes first, in a launch of
-				 * its own: when the others start it has published the 10th best of its
-				 * 4096 postings, and they emit a seventh of that.
-				 */
-				/*
-				 * The sparse + dense class (k_cold + k_scanm<.., DROP>) of a mixed batch is a few
-				 * thousand wavefronts: ALL of them fit the GPU at once, so no range ever finds a
-				 * threshold published by a higher one -- every range walks its cold phase and
-				 * pushes on a weak threshold (8 x the pending docs of the plain class).  The first
-				 * level(s) go ahead in a launch of their own here too.
-				 */
-				if (lev + 1 == cf.drop_split && (l.kind == 5 || l.kind == 9) && max_g > cf.drop_split && !big_k && !solo) {
-					launch_t l0 = l;
-					l0.count = (uint32_t)n_items - l0.first;
-					l0.q_first = o0;
-					l0.q_count = 0;			/* (no replay behind this one) */
-					l0.postings = 0;
-					wl.launches.push_back(l0);
-					l.first = (uint32_t)n_items;
-				}
-				if (lev == 0 && l.kind == 1 && l.nt_bucket == 1 && max_g >= cf.scan1_split && !big_k && !solo) {
-					launch_t l0 = l;
-					l0.count = (uint32_t)n_items - l0.first;
-					l0.q_first = o0;
-					l0.q_count = 0;			/* (no replay behind this one) */
-					l0.postings = 0;		/* (the class's postings are charged to the launch its queries end in) */
-					wl.launches.push_back(l0);
-					l.first = (uint32_t)n_items;
-				}
-			}
-		} else {
-			for (uint32_t oi = o0; oi < o1; oi++) {
-				const uint32_t i = order[oi];
-				for (uint32_t g = wl.qmeta[i].n_groups; g-- > 0; ) {
-					item_t it;
-					it.q = i;
-					it.g = g;
-					items[n_items++] = it;
-				}
-			}
-		}
-		l.count = (uint32_t)n_items - l.first;
-		l.q_first = o0;
-		l.q_count = o1 - o0;
-		l.postings = 0;
-		for (uint32_t oi = o0; oi < o1; oi++) {
-			const dev_query_t &dq = hq[order[oi]];
-			for (uint32_t t = 0; t < dq.nt; t++) {
-				/* (a dropped token whose list was replaced by its outlier list: the term's own df is not known
-				 * here any more -- the class's figure then counts what is scanned) */
-				l.postings += dq.pend[t] - dq.pbeg[t];
-			}
-		}
-		wl.launches.push_back(l);
-		o0 = o1;
-	}
-}
 
 /* the gathered record blocks, device -> mapped pinned host memory (8-byte words; blocks are multiples of 8) */
 __global__ void __launch_bounds__(256)
@@ -457,93 +22,148 @@ launch_cursors(nxsgpu_index_t *ix, const scan_args_t &a, const uint32_t *d_bnd_q
 }
 
 /*
- * One scan launch per query class.  With `ra` (top-k filter pass) the heap
+ * The scan kernel(s) of one class on stream `st`.  true: it ran on the mask path, whose overflowed
+ * ranges get a second chance on the accumulator tiles (launch_scan: launch_retry).
+ * (on_scan_stream: NXS_GPU_OLDSCAN / >= 2^31 docs put the generic kernel in place of the scan stream's
+ * kernels only -- the classes that run aside keep theirs)
+ */
+static bool
+launch_class(int MODE, const nxsgpu_index_t *ix, const launch_t &l, const scan_args_t &a, hipStream_t st,
+    bool on_scan_stream)
+{
+	const unsigned grid = l.count;
+	/* mask path / dense-term class: top-k filter pass only; the exact passes
+	 * (count, emit all) of these queries take the accumulator tiles */
+	const bool topk64 = MODE == MODE_TOPK && a.k >= 1 && a.k <= WAVE;
+
+	if (l.kind == CLS_GENERIC) {
+		nxs_launch_scan_generic(MODE, true, grid, st, a);
+	} else if (on_scan_stream && (ix->cfg.old_scan || ix->n_docs >= (1ull << 31))) {
+		nxs_launch_scan_generic(MODE, false, grid, st, a);
+	} else if (l.kind == CLS_TILES) {
+		if (l.nt_bucket == 1 && !ix->cfg.no_scan1) {
+			nxs_launch_scan1(MODE, grid, st, a);
+		} else {
+			nxs_launch_scan8(MODE, l.nt_bucket, l.nt_bucket == 1 ? (uint32_t)SHAPE_MASK : l.nomask, grid, st, a);
+		}
+	} else if (cls_mask_path(l.kind) && topk64) {
+		if (l.kind == CLS_SCANS) {
+			nxs_launch_scans(l.nt_bucket, l.nomask != SHAPE_OR, grid, st, a);
+		} else if (l.kind == CLS_SCANB) {
+			nxs_launch_scanb(l.nt_bucket, l.nomask != SHAPE_OR, false, grid, st, a);
+		} else {
+			nxs_launch_scanm(l.nt_bucket, l.nomask != SHAPE_OR, grid, st, a);
+		}
+		return true;
+	} else if (cls_sparse_dense(l.kind) && topk64 && !ix->cfg.drop_tiles) {
+		/* sparse + dense pure OR: top-k pass with the dense lists dropped */
+		nxs_launch_drop_class(l.nt_bucket, grid, st, a);
+		return true;
+	} else if (cls_mask_path(l.kind) || cls_sparse_dense(l.kind)) {
+		nxs_launch_scan8(MODE, l.nt_bucket, (cls_sparse_dense(l.kind) || l.nomask == SHAPE_OR) ? SHAPE_OR : SHAPE_MASK, grid, st, a);
+	} else if (l.kind == CLS_SCANQ && (topk64 || MODE == MODE_BIG)) {
+		nxs_launch_scanq(l.nt_bucket, grid, st, a);
+	} else if (cls_conjunctive(l.kind)) {
+		nxs_launch_scanr(MODE, l.nt_bucket, l.nomask == SHAPE_OR, grid, st, a);
+	}
+	return false;
+}
+
+/* what launch_scan does beyond the scans themselves (all zero: scans on the scan stream, nothing else) */
+struct scan_opts_t {
+	const replay_args_t *ra;	/* top-k filter pass: each class's heap replay follows its scan ... */
+	const uint32_t *d_qorder;	/* ... over the class's queries (worklist_t::qorder on the device) */
+	hipEvent_t	scans_done;	/* profiling: recorded on the scan stream behind the last scan */
+	bool		replays_aside;	/* the scan stream does not wait for the replays (the batch ends on replay_stream) */
+	hipStream_t	replay_stream;	/* NULL: nxsgpu_index::stream2 */
+	nxsgpu_index::dev_slot_t *prof_slot;	/* profiling: events around each class's scan kernels */
+	hipEvent_t	ahead_done;	/* the sparse + dense class's top ranges were sent ahead: the class waits for this */
+	hipStream_t	early_stream;	/* the conjunctive classes run here (NULL: on the scan stream) ... */
+	hipEvent_t	early_done;	/* ... and this is recorded behind them */
+};
+
+/*
+ * One scan launch per query class.  With `o.ra` (top-k filter pass) the heap
  * replay of a class is queued on the second stream as soon as the class's
  * scan is: the replay is a few latency-bound wavefronts (one per query) and
  * runs beside the next class's scan instead of after all of them.
  */
 static void
-launch_scan(int MODE, nxsgpu_index_t *ix, const scan_args_t &a0, const worklist_t &wl,
-    const replay_args_t *ra = NULL, const uint32_t *d_qorder = NULL, hipEvent_t scans_done = NULL,
-    bool replays_aside = false, hipStream_t replay_stream = NULL, nxsgpu_index::dev_slot_t *psl = NULL,
-    hipEvent_t ahead_done = NULL, hipStream_t early_stream = NULL, hipEvent_t early_done = NULL)
+launch_scan(int MODE, nxsgpu_index_t *ix, const scan_args_t &a0, const worklist_t &wl, const scan_opts_t &o)
 {
-	const hipStream_t st_rp = replay_stream ? replay_stream : ix->stream2;
+	const replay_args_t *const ra = o.ra;
+	const hipStream_t st_rp = o.replay_stream ? o.replay_stream : ix->stream2;
+	nxsgpu_index::dev_slot_t *const psl = o.prof_slot;
+	hipEvent_t scans_done = o.scans_done;
 	bool forked = false, forked3 = false, early_any = false;
+	const bool topk64 = MODE == MODE_TOPK && a0.k >= 1 && a0.k <= WAVE;
 	/* where the replay's heap lives: across the lanes (k <= 64) or in LDS (MODE_BIG) */
 	const int heap = a0.k <= WAVE ? HEAP_REG : HEAP_LDS;
 	const size_t heap_lds = heap == HEAP_LDS ? (size_t)a0.k * 8 : 0;
 	const launch_t *last_launch = NULL;
-	size_t n_launches = 0;
+	size_t n_launches = 0, n_late = 0;
 
 	for (const launch_t &l : wl.launches) {
 		n_launches += l.count != 0;
+		n_late += l.count && !cls_conjunctive(l.kind);
 	}
-	/* the sparse + dense class goes to its own stream when there is something to
-	 * run it beside (top-k pass only: its replay follows it there) */
-	const bool side3 = MODE == MODE_TOPK && ra && n_launches > 1 && a0.k >= 1 && a0.k <= WAVE && ix->cfg.drop_side;
 	/*
-	 * The conjunctive classes of a mixed batch (k_scanr, k_scanq: a few thousand latency-bound
-	 * wavefronts, 0.3 ms on the scan stream with the chip nearly idle) run EARLY: on the upload
+	 * Which stream a class goes to.
+	 * SIDE: the sparse + dense class goes to its own stream when there is something to
+	 * run it beside (top-k pass only: its replay follows it there).
+	 * EARLY: the conjunctive classes of a mixed batch (k_scanr, k_scanq: a few thousand latency-bound
+	 * wavefronts, 0.3 ms on the scan stream with the chip nearly idle) run on the upload
 	 * stream, behind this batch's k_cursors -- i.e. beside the previous batch's big scans --, their
 	 * heap replays with them; the batch's end waits for them (early_done).
-	 */
-	size_t n_late = 0;
-	for (const launch_t &l : wl.launches) {
-		n_late += l.count && !(l.kind == 3 || l.kind == 7);
-	}
-	/*
 	 * MODE_BIG, several batches in flight: the scan stream is what a step costs (one batch's scans
 	 * behind the other's; the replays -- milliseconds -- run aside, a stream per batch).  The
 	 * conjunctive classes and their short replays go to the batch's REPLAY stream, in front of the
 	 * other classes' replays: beside this batch's tile scans instead of behind them.
 	 */
-	const bool early_big = MODE == MODE_BIG && replays_aside && replay_stream && ra && n_late >= 1 && ix->cfg.and_early;
-	if (early_big) {
-		early_stream = st_rp;
-	}
-	const bool early_ok = early_big || (early_stream && early_done && MODE == MODE_TOPK && ra && n_late >= 1 &&
-	    a0.k >= 1 && a0.k <= WAVE);
+	const bool side3 = topk64 && ra && n_launches > 1 && ix->cfg.drop_side;
+	const bool early_big = MODE == MODE_BIG && o.replays_aside && o.replay_stream && ra && n_late >= 1 && ix->cfg.and_early;
+	const hipStream_t early_stream = early_big ? st_rp : o.early_stream;
+	const bool early_ok = early_big || (early_stream && o.early_done && topk64 && ra && n_late >= 1);
+	enum { ON_SCAN, ON_SIDE, ON_EARLY };
+	auto where = [&](const launch_t &l) -> int {
+		return (side3 && cls_sparse_dense(l.kind)) ? ON_SIDE : (early_ok && cls_conjunctive(l.kind)) ? ON_EARLY : ON_SCAN;
+	};
+
 	for (const launch_t &l : wl.launches) {
-		if (l.count && !(side3 && (l.kind == 5 || l.kind == 9)) && !(early_ok && (l.kind == 3 || l.kind == 7))) {
+		if (l.count && where(l) == ON_SCAN) {
 			last_launch = &l;
 		}
 	}
+	/* (MODE_BIG: the early classes first -- behind the cursors, which such a batch runs on the scan stream) */
 	std::vector<const launch_t *> seq;
 	seq.reserve(wl.launches.size());
 	if (early_big) {
-		bool any = false;
 		for (const launch_t &l : wl.launches) {
-			if (l.count && (l.kind == 3 || l.kind == 7)) {
+			if (l.count && cls_conjunctive(l.kind)) {
 				seq.push_back(&l);
-				any = true;
 			}
 		}
-		if (any) {	/* (behind the cursors, which a MODE_BIG batch runs on the scan stream) */
+		if (!seq.empty()) {
 			(void)hipEventRecord(ix->ev_fork3, ix->stream);
 			(void)hipStreamWaitEvent(st_rp, ix->ev_fork3, 0);
 		}
 	}
 	for (const launch_t &l : wl.launches) {
-		if (!(early_big && l.count && (l.kind == 3 || l.kind == 7))) {
+		if (!(early_big && l.count && cls_conjunctive(l.kind))) {
 			seq.push_back(&l);
 		}
 	}
 	for (const launch_t *lp : seq) {
 		const launch_t &l = *lp;
 		scan_args_t a = a0;
-		const unsigned grid = l.count;
-		/* mask path / dense-term class: top-k filter pass only; the exact passes
-		 * (count, emit all) of these queries take the accumulator tiles */
-		const bool topk64 = MODE == MODE_TOPK && a.k >= 1 && a.k <= WAVE;
 
 		if (l.count == 0) {
 			continue;
 		}
+		const int on = where(l);
+		const hipStream_t st = on == ON_SIDE ? ix->stream3 : on == ON_EARLY ? early_stream : ix->stream;
 		a.item_base = l.first;
 		/* profiling: events around this class's scan kernels, on the stream they go to */
-		const bool early = early_ok && (l.kind == 3 || l.kind == 7);
-		const hipStream_t cls_stream = (side3 && (l.kind == 5 || l.kind == 9)) ? ix->stream3 : early ? early_stream : ix->stream;
 		int pc = -1;
 		if (psl && psl->ev_cls_ok && psl->n_cls < NXSGPU_PROF_CLS && MODE_FILTERS(MODE)) {
 			pc = (int)psl->n_cls++;
@@ -551,123 +171,66 @@ launch_scan(int MODE, nxsgpu_index_t *ix, const scan_args_t &a0, const worklist_
 			psl->cls_key[pc] = l.kind << 8 | l.nomask << 4 | l.nt_bucket | (l.q_count == 0 && ra ? 0x80u : 0u);
 			psl->cls_post[pc] = l.postings;
 			psl->cls_q[pc] = l.q_count;
-			(void)hipEventRecord(psl->ev_cls[pc][0], cls_stream);
+			(void)hipEventRecord(psl->ev_cls[pc][0], st);
 		}
 		auto prof_stop = [&]() {
 			if (pc >= 0) {
-				(void)hipEventRecord(psl->ev_cls[pc][1], cls_stream);
+				(void)hipEventRecord(psl->ev_cls[pc][1], st);
 			}
 		};
 		/* (k_scanb<.., DROP>: up to five tokens) */
-		a.flags |= (l.kind == 5 && ix->cfg.drop_b && l.nt_bucket <= 5) ? 8u : 0u;
+		a.flags |= (l.kind == CLS_DROP_M && ix->cfg.drop_b && l.nt_bucket <= 5) ? SCAN_F_DROP_B : 0u;
+		a.flags |= l.kind == CLS_DROP_S ? SCAN_F_DROP_S : 0u;
 		/* this launch's retry list (mask path only) */
 		const size_t li = (size_t)(&l - wl.launches.data());
-		const bool retry = a0.retry_items && li < RETRY_LISTS && topk64 && (l.kind == 4 || l.kind == 5 || l.kind == 6 || l.kind == 8 || l.kind == 9);
+		const bool retry = a0.retry_items && li < RETRY_LISTS && topk64 && cls_has_retry(l.kind);
 		a.retry_count = retry ? a0.retry_count + li : NULL;
 		a.retry_items = retry ? a0.retry_items + li * RETRY_CAP : NULL;
 		a.retry_cap = retry ? RETRY_CAP : 0;
 		/* the ranges whose pending list overflowed, once more on the accumulator
 		 * tiles: a fixed, small grid whose wavefronts beyond the list's end return */
-		bool retry_pending = false;
-		auto launch_retry = [&](hipStream_t st) {
-			if (retry) {
-				scan_args_t a2 = a;
-				a2.flags |= 2;
-				nxs_launch_scan8(MODE_TOPK, l.nt_bucket, (l.kind == 5 || l.kind == 9 || l.nomask == 1) ? 1u : 0u, RETRY_CAP, st, a2);
-			}
+		auto launch_retry = [&](hipStream_t s) {
+			scan_args_t a2 = a;
+			a2.flags |= SCAN_F_RETRY;
+			nxs_launch_scan8(MODE_TOPK, l.nt_bucket, (cls_sparse_dense(l.kind) || l.nomask == SHAPE_OR) ? SHAPE_OR : SHAPE_MASK, RETRY_CAP, s, a2);
 		};
-		if (l.kind == 9) {
-			a.flags |= 16u;		/* the class's second kernel is k_scans<.., DROP> */
-		}
-		if (side3 && (l.kind == 5 || l.kind == 9)) {
-			replay_args_t r = *ra;
-			r.qlist = d_qorder + l.q_first;
+		if (on == ON_SIDE) {
 			if (!forked3) {
 				(void)hipEventRecord(ix->ev_fork3, ix->stream);
 				(void)hipStreamWaitEvent(ix->stream3, ix->ev_fork3, 0);
-				if (ahead_done) {
-					(void)hipStreamWaitEvent(ix->stream3, ahead_done, 0);	/* the class's top ranges (upload stream) */
+				if (o.ahead_done) {
+					(void)hipStreamWaitEvent(ix->stream3, o.ahead_done, 0);	/* the class's top ranges (upload stream) */
 				}
 				forked3 = true;
 			}
-			if (ix->cfg.drop_tiles) {
-				nxs_launch_scan8(MODE_TOPK, l.nt_bucket, 1u, grid, ix->stream3, a);
-				prof_stop();
-			} else {
-				a.flags |= ix->cfg.drop_prio ? 1u : 0u;
-				nxs_launch_drop_class(l.nt_bucket, grid, ix->stream3, a);
-				prof_stop();
-				launch_retry(ix->stream3);
-			}
-			if (l.q_count) {
-				nxs_launch_replay(HEAP_REG, l.q_count, 0, ix->stream3, r);
-			}
-			continue;
+			a.flags |= (ix->cfg.drop_prio && !ix->cfg.drop_tiles) ? SCAN_F_PRIO : 0u;
 		}
-		if (early) {
-			replay_args_t r = *ra;
-			r.qlist = d_qorder + l.q_first;
-			if (l.kind == 7 && (topk64 || MODE == MODE_BIG)) {
-				nxs_launch_scanq(l.nt_bucket, grid, early_stream, a);
-			} else {
-				nxs_launch_scanr(MODE, l.nt_bucket, l.nomask == 1, grid, early_stream, a);
-			}
+		bool retry_pending = launch_class(MODE, ix, l, a, st, on == ON_SCAN) && retry;
+		if (on != ON_SCAN) {
+			/* the class and its replay stay on their stream */
 			prof_stop();
-			if (l.q_count) {
-				nxs_launch_replay(heap, l.q_count, heap_lds, early_stream, r);
+			if (retry_pending) {
+				launch_retry(st);
 			}
-			early_any = true;
+			if (l.q_count) {
+				replay_args_t r = *ra;
+				r.qlist = o.d_qorder + l.q_first;
+				nxs_launch_replay(heap, l.q_count, heap_lds, st, r);
+			}
+			early_any = early_any || on == ON_EARLY;
 			continue;
 		}
-		if (l.kind == 0) {
-			nxs_launch_scan_generic(MODE, true, grid, ix->stream, a);
-		} else if (ix->cfg.old_scan || ix->n_docs >= (1ull << 31)) {
-			nxs_launch_scan_generic(MODE, false, grid, ix->stream, a);
-		} else if (l.kind == 1) {
-			if (l.nt_bucket == 1 && !ix->cfg.no_scan1) {
-				nxs_launch_scan1(MODE, grid, ix->stream, a);
-			} else {
-				nxs_launch_scan8(MODE, l.nt_bucket, l.nt_bucket == 1 ? 0u : l.nomask, grid, ix->stream, a);
-			}
-		} else if (l.kind == 4 || l.kind == 6 || l.kind == 8) {
-			if (topk64) {
-				if (l.kind == 8) {
-					nxs_launch_scans(l.nt_bucket, l.nomask != 1, grid, ix->stream, a);
-				} else if (l.kind == 6) {
-					nxs_launch_scanb(l.nt_bucket, l.nomask != 1, false, grid, ix->stream, a);
-				} else {
-					nxs_launch_scanm(l.nt_bucket, l.nomask != 1, grid, ix->stream, a);
-				}
-				/* (the second chance of its overflowed ranges: in front of the class's heap
-				 * replay, on the replay's stream -- not in front of the next class's scan) */
-				retry_pending = retry;
-				if (!(ra && l.q_count)) {
-					launch_retry(ix->stream);
-					retry_pending = false;
-				}
-			} else {
-				nxs_launch_scan8(MODE, l.nt_bucket, l.nomask == 1 ? 1u : 0u, grid, ix->stream, a);
-			}
-		} else if (l.kind == 5 || l.kind == 9) {
-			/* sparse + dense pure OR: top-k pass with the dense lists dropped */
-			if (topk64 && !ix->cfg.drop_tiles) {
-				nxs_launch_drop_class(l.nt_bucket, grid, ix->stream, a);
-				launch_retry(ix->stream);
-			} else {
-				nxs_launch_scan8(MODE, l.nt_bucket, 1u, grid, ix->stream, a);
-			}
-		} else if (l.kind == 3 || l.kind == 7) {
-			if (l.kind == 7 && (topk64 || MODE == MODE_BIG)) {
-				nxs_launch_scanq(l.nt_bucket, grid, ix->stream, a);
-			} else {
-				nxs_launch_scanr(MODE, l.nt_bucket, l.nomask == 1, grid, ix->stream, a);
-			}
+		/* (the second chance of the mask path's overflowed ranges: in front of the class's heap
+		 * replay, on the replay's stream -- not in front of the next class's scan) */
+		if (retry_pending && (cls_sparse_dense(l.kind) || !(ra && l.q_count))) {
+			launch_retry(st);
+			retry_pending = false;
 		}
 		prof_stop();
 		if (ra && l.q_count) {
 			replay_args_t r = *ra;
-			r.qlist = d_qorder + l.q_first;
-			if (&l == last_launch && !replays_aside) {
+			r.qlist = o.d_qorder + l.q_first;
+			if (&l == last_launch && !o.replays_aside) {
 				/* nothing left to run beside it: same stream, no event
 				 * round trip (a single query has only this one) */
 				if (retry_pending) {
@@ -687,17 +250,16 @@ launch_scan(int MODE, nxsgpu_index_t *ix, const scan_args_t &a0, const worklist_
 				nxs_launch_replay(heap, l.q_count, heap_lds, st_rp, r);
 				forked = true;
 			}
-			retry_pending = false;
 		}
 	}
 	if (scans_done) {
 		(void)hipEventRecord(scans_done, ix->stream);
 	}
 	if (early_any && !early_big) {
-		(void)hipEventRecord(early_done, early_stream);
-		(void)hipStreamWaitEvent(ix->stream, early_done, 0);
-		if (replays_aside) {
-			(void)hipStreamWaitEvent(st_rp, early_done, 0);		/* the batch ends there */
+		(void)hipEventRecord(o.early_done, early_stream);
+		(void)hipStreamWaitEvent(ix->stream, o.early_done, 0);
+		if (o.replays_aside) {
+			(void)hipStreamWaitEvent(st_rp, o.early_done, 0);		/* the batch ends there */
 		}
 	}
 	/*
@@ -706,14 +268,14 @@ launch_scan(int MODE, nxsgpu_index_t *ix, const scan_args_t &a0, const worklist_
 	 * stream does NOT wait for them -- the next batch's scans run beside this
 	 * batch's replays; the caller takes the batch's end from the replay stream.
 	 */
-	if (forked && !replays_aside) {
+	if (forked && !o.replays_aside) {
 		(void)hipEventRecord(ix->ev_join, st_rp);
 		(void)hipStreamWaitEvent(ix->stream, ix->ev_join, 0);
 	}
 	if (forked3) {
 		(void)hipEventRecord(ix->ev_join3, ix->stream3);
 		(void)hipStreamWaitEvent(ix->stream, ix->ev_join3, 0);
-		if (replays_aside) {
+		if (o.replays_aside) {
 			(void)hipStreamWaitEvent(st_rp, ix->ev_join3, 0);	/* the batch ends there */
 		}
 	}
@@ -950,6 +512,63 @@ struct cand_log_t {
 	uint32_t *	cnt;	/* [nq]; > cap = overflow */
 };
 
+/* the scan / replay arguments of a batch whose arrays are `L`; the callers add what is theirs alone
+ * (record fields, candidate log, the exact pass's offsets) */
+static scan_args_t
+make_scan_args(const nxsgpu_index_t *ix, int algo, const batch_layout_t &L, uint32_t k, uint32_t seg_cap)
+{
+	scan_args_t sa;
+
+	memset(&sa, 0, sizeof(sa));
+	sa.post = ix->d_post[algo];
+	sa.dense_col = ix->d_dense_col[algo];
+	sa.dense_stride = ix->n_docs;
+	sa.dense_q8 = algo == NXSGPU_BM25 ? ix->d_dense_q8 : NULL;
+	sa.dense_q8_stride = ix->dense_q8_stride;
+	sa.blkmap = ix->d_blkmap;
+	sa.bmrank = ix->d_bmrank;
+	sa.bm_words = ix->bm_words;
+	sa.n_docs = ix->n_docs;
+	sa.queries = L.q;
+	sa.qmeta = L.qmeta;
+	sa.items = L.items;
+	sa.k = k;
+	sa.seg_cap = seg_cap;
+	sa.seg_count = L.seg_count;
+	sa.cand_doc = L.cand_doc;
+	sa.cand_sc = L.cand_sc;
+	sa.overflow = L.ovf;
+	sa.cursors = L.cursors;
+	sa.pub = L.pub;
+	sa.pub_sk = L.pub_sk;
+	sa.cold_state = L.cold_state;
+	sa.cold_top = L.cold_top;
+	sa.retry_count = L.retry_cnt;
+	sa.retry_items = L.retry_items;
+	return sa;
+}
+
+static replay_args_t
+make_replay_args(const nxsgpu_index_t *ix, const batch_layout_t &L, uint32_t k, uint32_t seg_cap)
+{
+	replay_args_t ra;
+
+	memset(&ra, 0, sizeof(ra));
+	ra.flags = ix->cfg.old_replay ? REPLAY_F_ONE_LANE : 0u;
+	ra.qmeta = L.qmeta;
+	ra.seg_cap = seg_cap;
+	ra.seg_count = L.seg_count;
+	ra.cand_doc = L.cand_doc;
+	ra.cand_sc = L.cand_sc;
+	ra.doc_ids = ix->d_doc_ids;
+	ra.k = k;
+	ra.out_ids = L.out_ids;
+	ra.out_sc = L.out_sc;
+	ra.out_count = L.out_cnt;
+	ra.skip = L.ovf;
+	return ra;
+}
+
 static int
 search_impl(nxsgpu_index_t *ix, int algo, uint64_t limit, const nxsgpu_query_t *queries,
     uint32_t nq, nxsgpu_results_t *res, cand_log_t *cl = NULL)
@@ -963,13 +582,6 @@ search_impl(nxsgpu_index_t *ix, int algo, uint64_t limit, const nxsgpu_query_t *
 	std::vector<uint32_t> h_ovf, h_cnt;
 	worklist_t wl;
 	uint64_t total_post = 0;
-	uint8_t *p;
-	dev_query_t *d_q;
-	qmeta_t *d_qmeta;
-	item_t *d_items;
-	uint32_t *d_seg_count, *d_cand_doc, *d_ovf, *d_cnt;
-	uint64_t *d_ids;
-	float *d_cand_sc, *d_sc;
 	scan_args_t sa;
 	replay_args_t ra;
 	const uint32_t kfast = fast ? (uint32_t)limit : NXSGPU_FAST_K;
@@ -997,23 +609,6 @@ search_impl(nxsgpu_index_t *ix, int algo, uint64_t limit, const nxsgpu_query_t *
 		return 0;
 	}
 
-	uint64_t *d_log_ids = NULL;
-	float *d_log_sc = NULL;
-	uint32_t *d_log_cnt = NULL, *d_log_slot = NULL;
-	struct log_guard_t {
-		uint64_t *&a; float *&b; uint32_t *&c; uint32_t *&d;
-		~log_guard_t() { (void)hipFree(a); (void)hipFree(b); (void)hipFree(c); (void)hipFree(d); }
-	} log_guard{d_log_ids, d_log_sc, d_log_cnt, d_log_slot};
-	if (cl) {
-		if (hipMalloc((void **)&d_log_ids, (size_t)nq * cl->cap * 8 + 8) != hipSuccess ||
-		    hipMalloc((void **)&d_log_sc, (size_t)nq * cl->cap * 4 + 4) != hipSuccess ||
-		    hipMalloc((void **)&d_log_cnt, (size_t)nq * 4) != hipSuccess ||
-		    hipMalloc((void **)&d_log_slot, (size_t)nq * 4) != hipSuccess ||
-		    hipMemsetAsync(d_log_cnt, 0, (size_t)nq * 4, ix->stream) != hipSuccess) {
-			set_error("hipMalloc for the candidate log failed");
-			return -1;
-		}
-	}
 	/* (this blocking path is also where queries land whose candidate lists
 	 * overflowed in a batch: no sparse + dense class here -- its pending list is
 	 * what overflows, and the tiles take such a query without emitting every match
@@ -1024,94 +619,44 @@ search_impl(nxsgpu_index_t *ix, int algo, uint64_t limit, const nxsgpu_query_t *
 	build_worklist(ix, hq.data(), nq, wl, false, big ? (uint32_t)limit : 0);
 	const uint64_t nseg = wl.n_segs;
 
-	/* workspace: queries | meta | items | seg_count | overflow | candidates | outputs */
-	{
-		size_t need = 8192 + nq * 4 + nq * sizeof(dev_query_t) + nq * sizeof(qmeta_t)
-		    + nseg * sizeof(item_t) + nseg * 4 + nq * 4
-		    + (nseg + nq) * 4 * (1 + NXSGPU_MAX_TOKENS) + nseg * 4 + 1024
-		    + nseg * seg_cap * 8 + (size_t)nq * kfast * 12 + nq * 4 + 16 * 256
-		    + nseg * (16 * 4 + 64 * 4) + 1024 + RETRY_LISTS * (4 + RETRY_CAP * sizeof(item_t)) + 1024
-		    + (big ? nseg * 32 + 256 : 0);
-		if (!ensure_ws(ix, need)) {
-			return -1;
-		}
-	}
 	/*
 	 * Everything the kernels read from the host is one contiguous block, staged
-	 * in pinned memory and uploaded by ONE copy (the two zero-filled arrays
+	 * in pinned memory and uploaded by ONE copy (the zero-filled arrays
 	 * included); the flags and the results are one block and ONE copy back.  A
 	 * single query used to pay eleven small pageable copies + two memsets:
 	 * most of its latency.
 	 */
-	p = (uint8_t *)ix->ws;
-	uint8_t *const up0 = p;
-	d_q = carve<dev_query_t>(p, nq);
-	d_qmeta = carve<qmeta_t>(p, nq);
-	d_items = carve<item_t>(p, nseg);
-	uint32_t *d_bnd_q = carve<uint32_t>(p, nseg + nq);
-	uint32_t *d_qorder = carve<uint32_t>(p, nq);
-	float *d_pub = carve<float>(p, nseg);
-	uint32_t *d_retry_cnt = carve<uint32_t>(p, RETRY_LISTS);
-	d_ovf = carve<uint32_t>(p, nq);
-	const size_t up_len = (size_t)(p - up0);
-	uint8_t *const down0 = (uint8_t *)d_ovf;
-	d_ids = carve<uint64_t>(p, (size_t)nq * kfast);
-	d_sc = carve<float>(p, (size_t)nq * kfast);
-	d_cnt = carve<uint32_t>(p, nq);
-	const size_t down_len = (size_t)(p - down0);
-	d_seg_count = carve<uint32_t>(p, nseg);
-	uint32_t *d_cursors = carve<uint32_t>(p, (nseg + nq) * NXSGPU_MAX_TOKENS);
-	d_cand_doc = carve<uint32_t>(p, nseg * seg_cap);
-	d_cand_sc = carve<float>(p, nseg * seg_cap);
-	uint32_t *d_cold_state = carve<uint32_t>(p, nseg * 16);
-	float *d_cold_top = carve<float>(p, nseg * 64);
-	item_t *d_retry_items = carve<item_t>(p, RETRY_LISTS * RETRY_CAP);
-	float *d_pub_sk = carve<float>(p, big ? nseg * 8 : 0);
-
-	if (!ensure_pin(ix, up_len + down_len + 512)) {
+	batch_dims_t dims;
+	memset(&dims, 0, sizeof(dims));
+	dims.nq = nq;
+	dims.nseg = nseg;
+	dims.seg_cap = seg_cap;
+	dims.k = kfast;
+	dims.big = big;
+	dims.results = true;
+	dims.log_cap = cl ? cl->cap : 0;
+	const batch_layout_t sizes = batch_layout(NULL, dims);
+	if (!ensure_ws(ix, sizes.len + 8192) || !ensure_pin(ix, sizes.host_len + 512)) {
 		return -1;
 	}
-	uint8_t *const h_up = (uint8_t *)ix->h_pin;
-	uint8_t *const h_down = (uint8_t *)(((uintptr_t)h_up + up_len + 255) & ~(uintptr_t)255);
-	memset(h_up, 0, up_len);
-	memcpy(h_up + ((uint8_t *)d_q - up0), hq.data(), nq * sizeof(dev_query_t));
-	memcpy(h_up + ((uint8_t *)d_qmeta - up0), wl.qmeta.data(), nq * sizeof(qmeta_t));
-	memcpy(h_up + ((uint8_t *)d_items - up0), wl.items.data(), nseg * sizeof(item_t));
-	memcpy(h_up + ((uint8_t *)d_bnd_q - up0), wl.bnd_q.data(), (nseg + nq) * 4);
-	memcpy(h_up + ((uint8_t *)d_qorder - up0), wl.qorder.data(), nq * 4);
-	if (hipMemcpyAsync(up0, h_up, up_len, hipMemcpyHostToDevice, ix->stream) != hipSuccess) {
+	const batch_layout_t D = batch_layout((uint8_t *)ix->ws, dims), H = batch_layout((uint8_t *)ix->h_pin, dims);
+	memset(H.q, 0, H.up_len);
+	memcpy(H.q, hq.data(), nq * sizeof(dev_query_t));
+	memcpy(H.qmeta, wl.qmeta.data(), nq * sizeof(qmeta_t));
+	memcpy(H.items, wl.items.data(), nseg * sizeof(item_t));
+	memcpy(H.bnd_q, wl.bnd_q.data(), (nseg + nq) * 4);
+	memcpy(H.qorder, wl.qorder.data(), nq * 4);
+	if (hipMemcpyAsync(D.q, H.q, D.up_len, hipMemcpyHostToDevice, ix->stream) != hipSuccess) {
 		set_error("query upload failed");
 		return -1;
 	}
+	if (cl && hipMemsetAsync(D.log_cnt, 0, (size_t)nq * 4, ix->stream) != hipSuccess) {
+		set_error("memset failed");
+		return -1;
+	}
 
-	memset(&sa, 0, sizeof(sa));
-	sa.post = ix->d_post[algo];
-	sa.dense_col = ix->d_dense_col[algo];
-	sa.dense_stride = ix->n_docs;
-	sa.dense_q8 = algo == NXSGPU_BM25 ? ix->d_dense_q8 : NULL;
-	sa.dense_q8_stride = ix->dense_q8_stride;
-	sa.blkmap = ix->d_blkmap;
-	sa.bmrank = ix->d_bmrank;
-	sa.bm_words = ix->bm_words;
-	sa.queries = d_q;
-	sa.n_docs = ix->n_docs;
-	sa.qmeta = d_qmeta;
-	sa.items = d_items;
-	sa.k = kfast;
-	sa.seg_cap = seg_cap;
-	sa.seg_count = d_seg_count;
-	sa.seg_off = NULL;
-	sa.cand_doc = d_cand_doc;
-	sa.cand_sc = d_cand_sc;
-	sa.overflow = d_ovf;
-	sa.cursors = d_cursors;
-	sa.pub = d_pub;
-	sa.cold_state = d_cold_state;
-	sa.cold_top = d_cold_top;
-	sa.retry_count = d_retry_cnt;
-	sa.retry_items = d_retry_items;
-	sa.pub_sk = d_pub_sk;
-	if (big && hipMemsetAsync(d_pub_sk, 0, nseg * 32, ix->stream) != hipSuccess) {
+	sa = make_scan_args(ix, algo, D, kfast, seg_cap);
+	if (big && hipMemsetAsync(D.pub_sk, 0, nseg * 32, ix->stream) != hipSuccess) {
 		set_error("memset failed");
 		return -1;
 	}
@@ -1119,41 +664,34 @@ search_impl(nxsgpu_index_t *ix, int algo, uint64_t limit, const nxsgpu_query_t *
 	h_ovf.assign(nq, 0);
 	if (fast) {
 		if (ix->profiling) (void)hipEventRecord(ix->ev[0], ix->stream);
-		launch_cursors(ix, sa, d_bnd_q, (uint32_t)(nseg + nq));
-		memset(&ra, 0, sizeof(ra));
-		ra.flags = ix->cfg.old_replay ? 1u : 0u;
-		ra.qmeta = d_qmeta;
-		ra.seg_cap = seg_cap;
-		ra.seg_count = d_seg_count;
-		ra.cand_doc = d_cand_doc;
-		ra.cand_sc = d_cand_sc;
-		ra.doc_ids = ix->d_doc_ids;
-		ra.k = kfast;
-		ra.out_ids = d_ids;
-		ra.out_sc = d_sc;
-		ra.out_count = d_cnt;
-		ra.skip = d_ovf;
+		launch_cursors(ix, sa, D.bnd_q, (uint32_t)(nseg + nq));
+		ra = make_replay_args(ix, D, kfast, seg_cap);
 		if (cl) {
-			ra.log_ids = d_log_ids;
-			ra.log_sc = d_log_sc;
-			ra.log_cnt = d_log_cnt;
+			ra.log_ids = D.log_ids;
+			ra.log_sc = D.log_sc;
+			ra.log_cnt = D.log_cnt;
 			ra.log_cap = cl->cap;
 		}
+		scan_opts_t so;
+		memset(&so, 0, sizeof(so));
 		if (ix->cfg.one_replay) {
-			launch_scan(big ? MODE_BIG : MODE_TOPK, ix, sa, wl);
+			launch_scan(big ? MODE_BIG : MODE_TOPK, ix, sa, wl, so);
 			if (ix->profiling) (void)hipEventRecord(ix->ev[1], ix->stream);
 			nxs_launch_replay(big ? HEAP_LDS : HEAP_REG, nq, big ? (size_t)limit * 8 : 0, ix->stream, ra);
 		} else {
 			/* (profile: "replay" is then only what the last class's replay
 			 * adds after the last scan) */
-			launch_scan(big ? MODE_BIG : MODE_TOPK, ix, sa, wl, &ra, d_qorder, ix->profiling ? ix->ev[1] : NULL);
+			so.ra = &ra;
+			so.d_qorder = D.qorder;
+			so.scans_done = ix->profiling ? ix->ev[1] : NULL;
+			launch_scan(big ? MODE_BIG : MODE_TOPK, ix, sa, wl, so);
 		}
 		if (ix->profiling) (void)hipEventRecord(ix->ev[2], ix->stream);
 		if (hipGetLastError() != hipSuccess) {
 			set_error("kernel launch failed");
 			return -1;
 		}
-		if (hipMemcpyAsync(h_down, down0, down_len, hipMemcpyDeviceToHost, ix->stream) != hipSuccess) {
+		if (hipMemcpyAsync(H.ovf, D.ovf, D.down_len, hipMemcpyDeviceToHost, ix->stream) != hipSuccess) {
 			set_error("copy failed");
 			return -1;
 		}
@@ -1172,10 +710,10 @@ search_impl(nxsgpu_index_t *ix, int algo, uint64_t limit, const nxsgpu_query_t *
 	if (fast) {
 		f_ids.resize((size_t)nq * kfast);
 		f_sc.resize((size_t)nq * kfast);
-		memcpy(h_ovf.data(), h_down + ((uint8_t *)d_ovf - down0), nq * 4);
-		memcpy(f_ids.data(), h_down + ((uint8_t *)d_ids - down0), f_ids.size() * 8);
-		memcpy(f_sc.data(), h_down + ((uint8_t *)d_sc - down0), f_sc.size() * 4);
-		memcpy(h_cnt.data(), h_down + ((uint8_t *)d_cnt - down0), nq * 4);
+		memcpy(h_ovf.data(), H.ovf, nq * 4);
+		memcpy(f_ids.data(), H.out_ids, f_ids.size() * 8);
+		memcpy(f_sc.data(), H.out_sc, f_sc.size() * 4);
+		memcpy(h_cnt.data(), H.out_cnt, nq * 4);
 	}
 	/* (a re-run beside batches in flight stays out of the per-launch averages: with
 	 * it in, one overflowed query per step halved the "kernel_ms" bench.py prints) */
@@ -1215,7 +753,7 @@ search_impl(nxsgpu_index_t *ix, int algo, uint64_t limit, const nxsgpu_query_t *
 		for (uint32_t j = 0; j < nx; j++) {
 			xhq[j] = hq[xq[j]];
 		}
-		build_worklist(ix, xhq.data(), nx, xwl);
+		build_worklist(ix, xhq.data(), nx, xwl, false, 0);
 		const uint64_t xseg = xwl.n_segs;
 		std::vector<uint32_t> sc_cnt(xseg);
 		std::vector<uint64_t> sc_off(xseg + 1, 0), hp_off(nx + 1, 0), o_off(nx + 1, 0);
@@ -1263,7 +801,8 @@ search_impl(nxsgpu_index_t *ix, int algo, uint64_t limit, const nxsgpu_query_t *
 		sa.cursors = dx_cursors;
 		sa.k = 0xffffffffu;
 		launch_cursors(ix, sa, dx_bnd_q, (uint32_t)(xseg + nx));
-		launch_scan(MODE_COUNT, ix, sa, xwl);
+		const scan_opts_t scans_only = {};
+		launch_scan(MODE_COUNT, ix, sa, xwl, scans_only);
 		if (hipMemcpyAsync(sc_cnt.data(), dx_seg_count, xseg * 4, hipMemcpyDeviceToHost, ix->stream) != hipSuccess ||
 		    hipStreamSynchronize(ix->stream) != hipSuccess) {
 			set_error("count pass failed: %s", hipGetErrorString(hipGetLastError()));
@@ -1313,16 +852,14 @@ search_impl(nxsgpu_index_t *ix, int algo, uint64_t limit, const nxsgpu_query_t *
 			sb.seg_off = dx_seg_off;
 			sb.cand_doc = dx_cdoc;
 			sb.cand_sc = dx_csc;
-			launch_scan(MODE_ALL, ix, sb, xwl);
-			memset(&ra, 0, sizeof(ra));
-			ra.flags = ix->cfg.old_replay ? 1u : 0u;
+			launch_scan(MODE_ALL, ix, sb, xwl, scans_only);
+			/* (segments addressed by seg_off, heaps in global memory, results at out_off; nothing is skipped) */
+			ra = make_replay_args(ix, D, (uint32_t)std::min<uint64_t>(limit, 0xffffffffu), 0);
 			ra.qmeta = dx_qmeta;
-			ra.seg_cap = 0;
+			ra.seg_count = NULL;
 			ra.seg_off = dx_seg_off;
 			ra.cand_doc = dx_cdoc;
 			ra.cand_sc = dx_csc;
-			ra.doc_ids = ix->d_doc_ids;
-			ra.k = (uint32_t)std::min<uint64_t>(limit, 0xffffffffu);
 			ra.gheap_s = dx_hs;
 			ra.gheap_d = dx_hd;
 			ra.heap_off = dx_hoff;
@@ -1330,17 +867,18 @@ search_impl(nxsgpu_index_t *ix, int algo, uint64_t limit, const nxsgpu_query_t *
 			ra.out_sc = dx_sc;
 			ra.out_count = dx_cnt;
 			ra.out_off = dx_ooff;
+			ra.skip = NULL;
 			if (cl) {
 				/* row of the log = the query's index in the whole batch */
-				if (hipMemcpyAsync(d_log_slot, xq.data(), (size_t)nx * 4, hipMemcpyHostToDevice, ix->stream) != hipSuccess) {
+				if (hipMemcpyAsync(D.log_slot, xq.data(), (size_t)nx * 4, hipMemcpyHostToDevice, ix->stream) != hipSuccess) {
 					set_error("upload failed");
 					break;
 				}
-				ra.log_ids = d_log_ids;
-				ra.log_sc = d_log_sc;
-				ra.log_cnt = d_log_cnt;
+				ra.log_ids = D.log_ids;
+				ra.log_sc = D.log_sc;
+				ra.log_cnt = D.log_cnt;
 				ra.log_cap = cl->cap;
-				ra.log_slot = d_log_slot;
+				ra.log_slot = D.log_slot;
 			}
 			if (ra.k <= REPLAY_LDS_K) {
 				nxs_launch_replay(HEAP_LDS, nx, (size_t)ra.k * 8, ix->stream, ra);
@@ -1371,9 +909,9 @@ search_impl(nxsgpu_index_t *ix, int algo, uint64_t limit, const nxsgpu_query_t *
 	}
 
 	if (cl) {
-		if (hipMemcpyAsync(cl->ids, d_log_ids, (size_t)nq * cl->cap * 8, hipMemcpyDeviceToHost, ix->stream) != hipSuccess ||
-		    hipMemcpyAsync(cl->sc, d_log_sc, (size_t)nq * cl->cap * 4, hipMemcpyDeviceToHost, ix->stream) != hipSuccess ||
-		    hipMemcpyAsync(cl->cnt, d_log_cnt, (size_t)nq * 4, hipMemcpyDeviceToHost, ix->stream) != hipSuccess ||
+		if (hipMemcpyAsync(cl->ids, D.log_ids, (size_t)nq * cl->cap * 8, hipMemcpyDeviceToHost, ix->stream) != hipSuccess ||
+		    hipMemcpyAsync(cl->sc, D.log_sc, (size_t)nq * cl->cap * 4, hipMemcpyDeviceToHost, ix->stream) != hipSuccess ||
+		    hipMemcpyAsync(cl->cnt, D.log_cnt, (size_t)nq * 4, hipMemcpyDeviceToHost, ix->stream) != hipSuccess ||
 		    hipStreamSynchronize(ix->stream) != hipSuccess) {
 			set_error("candidate log copy failed");
 			return -1;
@@ -1606,8 +1144,7 @@ batch_begin(nxsgpu_index_t *ix, int algo, uint32_t limit, const nxsgpu_query_t *
 	const bool solo = nq <= 64 && !others && !gather;
 	/* (limits > 64: the upload stream's hardware queue carries every third batch's replays --
 	 * milliseconds --, so these batches' plans and cursors go up on the scan stream) */
-	const bool big_b = limit > NXSGPU_FAST_K;
-	hipStream_t s_up = (solo || big_b) ? ix->stream : ix->stream_up;
+	hipStream_t s_up = (solo || big) ? ix->stream : ix->stream_up;
 	/* the records come down on their own stream only when there is a collective
 	 * to run beside the next batch's scans; a plain 135 KB copy rides the scan
 	 * stream (a separate stream showed sporadic 5-20 ms host stalls in the copy
@@ -1655,23 +1192,28 @@ batch_begin(nxsgpu_index_t *ix, int algo, uint32_t limit, const nxsgpu_query_t *
 	 * block and fills the status words itself before the launch.
 	 */
 	/* (the block as part of the batch's one upload -- zeroed and filled on the host, the all-gather's send buffer where
-	 * it lies in the workspace: measured for sharded batches, 770k -> 650k queries/s, `_begin` 0.3 ms longer -- not the
-	 * host's writes (pinned memory zeroes at 117 GB/s here, like pageable); the device-side memset stays) */
-	const bool block_in_ws = false;
+	 * it lies in the workspace -- was tried and is gone: measured for sharded batches, 770k -> 650k queries/s, `_begin`
+	 * 0.3 ms longer -- not the host's writes (pinned memory zeroes at 117 GB/s here, like pageable); the device-side
+	 * memset stays.  NOTES.md: "The record block as part of the batch's one upload") */
 	const bool block_on_host = o.records && !gather;
 
 	/* plans straight into the pinned staging area (room for the work list:
-	 * <= target + nq ranges, see build_worklist) */
-	const uint64_t wave_target = 4 * std::max(ix->cfg.wave_target, ix->cfg.wave_target_scans);	/* (build_worklist: target_eff) */
-	const size_t seg_bound = (size_t)wave_target + 2 * (size_t)nq + 64;
-	const size_t stage_need = 32768 + RETRY_LISTS * 4 + 256 + nq * (sizeof(dev_query_t) + sizeof(qmeta_t) + 16)
-	    + seg_bound * (sizeof(item_t) + 8) + nq * 4 + NXSGPU_STATUS_WORDS(o.n_slots) * 4 + 4096
-	    + (block_in_ws ? sl->block_bytes : 0);	/* (the record block itself lives in h_blocks) */
-	if (slot_ensure(*sl, 0, stage_need) != 0) {
+	 * <= target + nq ranges, see size_ranges) */
+	const uint64_t wave_target = 4 * std::max(ix->cfg.wave_target, ix->cfg.wave_target_scans);	/* (size_ranges: target_eff) */
+	batch_dims_t dims;
+	memset(&dims, 0, sizeof(dims));
+	dims.nq = nq;
+	dims.nseg = (size_t)wave_target + 2 * (size_t)nq + 64;
+	dims.seg_cap = seg_cap;
+	dims.k = limit;
+	dims.big = big;
+	dims.rec_slots = o.records;
+	dims.status_words = o.records ? NXSGPU_STATUS_WORDS(o.n_slots) : 0;
+	const uint64_t seg_bound = dims.nseg;
+	if (slot_ensure(*sl, 0, batch_layout(NULL, dims).host_len + 32768) != 0) {
 		return -1;
 	}
-	uint8_t *hp = sl->h_stage;
-	dev_query_t *h_q = carve<dev_query_t>(hp, nq);
+	dev_query_t *const h_q = batch_layout(sl->h_stage, dims).q;
 	if (fill_dev_queries(ix, algo, queries, nq, h_q, total_post, !big) != 0) {
 		return -1;
 	}
@@ -1680,48 +1222,39 @@ batch_begin(nxsgpu_index_t *ix, int algo, uint32_t limit, const nxsgpu_query_t *
 	tb1 = now_us();
 	const uint64_t nseg = wl.n_segs;
 	if (nseg > seg_bound) {
-		set_error("work list larger than its bound (%llu > %zu)", (unsigned long long)nseg, seg_bound);
+		set_error("work list larger than its bound (%llu > %llu)", (unsigned long long)nseg, (unsigned long long)seg_bound);
 		return -1;
 	}
 	/*
-	 * Everything the kernels read from the host -- the zero-filled flag, threshold
-	 * and record arrays included -- is ONE block and ONE copy up.
+	 * Everything the kernels read from the host -- the zero-filled flag and threshold
+	 * arrays included -- is ONE block and ONE copy up: the staging area and the device
+	 * workspace have the same layout, the uploaded block first, then what only the
+	 * kernels touch.
 	 */
-	qmeta_t *h_qmeta = carve<qmeta_t>(hp, nq);
-	item_t *h_items = carve<item_t>(hp, nseg);
-	uint32_t *h_bnd_q = carve<uint32_t>(hp, nseg + nq);
-	uint32_t *h_qorder = carve<uint32_t>(hp, nq);
-	uint32_t *h_recslot = carve<uint32_t>(hp, nq);
-	uint32_t *h_ovf = carve<uint32_t>(hp, nq);
-	float *h_pub = carve<float>(hp, nseg);
-	uint32_t *h_retry_cnt = carve<uint32_t>(hp, RETRY_LISTS);
-	uint8_t *h_block = carve<uint8_t>(hp, block_in_ws ? sl->block_bytes : 0);
-	const size_t up_len = (size_t)(hp - sl->h_stage);
-	uint32_t *h_status = block_in_ws ? (uint32_t *)(h_block + recs_len) : carve<uint32_t>(hp, NXSGPU_STATUS_WORDS(o.n_slots));
-	if ((size_t)(hp - sl->h_stage) > sl->h_stage_len) {
-		set_error("staging area too small (%zu > %zu)", (size_t)(hp - sl->h_stage), sl->h_stage_len);
+	dims.nseg = nseg;
+	const batch_layout_t H = batch_layout(sl->h_stage, dims);
+	if (H.host_len > sl->h_stage_len) {
+		set_error("staging area too small (%zu > %zu)", H.host_len, sl->h_stage_len);
 		return -1;
 	}
 	if (nq) {
-		memcpy(h_qmeta, wl.qmeta.data(), nq * sizeof(qmeta_t));
-		memcpy(h_items, wl.items.data(), nseg * sizeof(item_t));
-		memcpy(h_bnd_q, wl.bnd_q.data(), (nseg + nq) * 4);
-		memcpy(h_qorder, wl.qorder.data(), nq * 4);
-		memset(h_ovf, 0, nq * 4);
-		memset(h_pub, 0, nseg * 4);
+		memcpy(H.qmeta, wl.qmeta.data(), nq * sizeof(qmeta_t));
+		memcpy(H.items, wl.items.data(), nseg * sizeof(item_t));
+		memcpy(H.bnd_q, wl.bnd_q.data(), (nseg + nq) * 4);
+		memcpy(H.qorder, wl.qorder.data(), nq * 4);
+		memset(H.ovf, 0, nq * 4);
+		memset(H.pub, 0, nseg * 4);
 	}
-	memset(h_retry_cnt, 0, RETRY_LISTS * 4);
-	sl->h_ovf = h_ovf;
+	memset(H.retry_cnt, 0, RETRY_LISTS * 4);
+	sl->h_ovf = H.ovf;
+	uint32_t *h_status = H.status;
 	if (o.records) {
 		for (uint32_t i = 0; i < nq; i++) {
 			if (o.slot_of_plan[i] >= o.n_slots) {
 				set_error("plan %u: record slot %u out of range", i, o.slot_of_plan[i]);
 				return -1;
 			}
-			h_recslot[i] = o.slot_of_plan[i];
-		}
-		if (block_in_ws) {
-			memset(h_block, 0, sl->block_bytes);
+			H.rec_slot[i] = o.slot_of_plan[i];
 		}
 		if (block_on_host) {
 			/* (the slot's previous batch was collected: nothing reads it any more) */
@@ -1743,46 +1276,20 @@ batch_begin(nxsgpu_index_t *ix, int algo, uint32_t limit, const nxsgpu_query_t *
 		}
 	}
 
-	/* device workspace: the uploaded block first (same carve sequence => same
-	 * offsets), then what only the kernels touch */
-	const size_t ws_need = 32768 + up_len + nseg * 4
-	    + (nseg + nq) * 4 * NXSGPU_MAX_TOKENS + nseg * (size_t)seg_cap * 8 + nseg * (16 * 4 + 64 * 4)
-	    + RETRY_LISTS * RETRY_CAP * sizeof(item_t) + 1024 + (big ? nseg * 32 + 256 : 0);
-	if (slot_ensure(*sl, ws_need, 0) != 0) {
+	if (slot_ensure(*sl, batch_layout(NULL, dims).len + 32768, 0) != 0) {
 		return -1;
 	}
-	uint8_t *p = (uint8_t *)sl->ws;
-	dev_query_t *d_q = carve<dev_query_t>(p, nq);
-	qmeta_t *d_qmeta = carve<qmeta_t>(p, nq);
-	item_t *d_items = carve<item_t>(p, nseg);
-	uint32_t *d_bnd_q = carve<uint32_t>(p, nseg + nq);
-	uint32_t *d_qorder = carve<uint32_t>(p, nq);
-	uint32_t *d_recslot = carve<uint32_t>(p, nq);
-	uint32_t *d_ovf = carve<uint32_t>(p, nq);
-	float *d_pub = carve<float>(p, nseg);
-	uint32_t *d_retry_cnt = carve<uint32_t>(p, RETRY_LISTS);
-	uint8_t *d_myblock = carve<uint8_t>(p, block_in_ws ? sl->block_bytes : 0);
-	uint32_t *d_seg_count = carve<uint32_t>(p, nseg);
-	uint32_t *d_cursors = carve<uint32_t>(p, (nseg + nq) * NXSGPU_MAX_TOKENS);
-	uint32_t *d_cand_doc = carve<uint32_t>(p, nseg * (size_t)seg_cap);
-	float *d_cand_sc = carve<float>(p, nseg * (size_t)seg_cap);
-	uint32_t *d_cold_state = carve<uint32_t>(p, nseg * 16);
-	float *d_cold_top = carve<float>(p, nseg * 64);
-	item_t *d_retry_items = carve<item_t>(p, RETRY_LISTS * RETRY_CAP);
-	float *d_pub_sk = carve<float>(p, big ? nseg * 8 : 0);
-	if (block_on_host) {
-		d_myblock = sl->h_blocks_dev;
-	} else if (o.records && !block_in_ws) {
-		d_myblock = sl->d_blocks + (size_t)my_rank * sl->block_bytes;
-	}
+	const batch_layout_t D = batch_layout((uint8_t *)sl->ws, dims);
+	uint8_t *const d_myblock = !o.records ? NULL : block_on_host ? sl->h_blocks_dev :
+	    sl->d_blocks + (size_t)my_rank * sl->block_bytes;
 
 	sl->seq = ++ix->slot_seq;
 	tb2 = now_us();
-	if (hipMemcpyAsync(sl->ws, sl->h_stage, up_len, hipMemcpyHostToDevice, s_up) != hipSuccess) {
+	if (hipMemcpyAsync(D.q, H.q, D.up_len, hipMemcpyHostToDevice, s_up) != hipSuccess) {
 		set_error("query upload failed");
 		return begin_fail(ix);
 	}
-	if (o.records && !block_in_ws && !block_on_host) {
+	if (o.records && !block_on_host) {
 		if ((recs_len && hipMemsetAsync(d_myblock, 0, recs_len, s_up) != hipSuccess) ||
 		    hipMemcpyAsync(d_myblock + recs_len, h_status, NXSGPU_STATUS_WORDS(o.n_slots) * 4,
 		    hipMemcpyHostToDevice, s_up) != hipSuccess) {
@@ -1792,54 +1299,18 @@ batch_begin(nxsgpu_index_t *ix, int algo, uint32_t limit, const nxsgpu_query_t *
 	}
 
 	tc[0] = now_us();
-	scan_args_t sa;
-	replay_args_t ra;
-	memset(&sa, 0, sizeof(sa));
-	sa.post = ix->d_post[algo];
-	sa.dense_col = ix->d_dense_col[algo];
-	sa.dense_stride = ix->n_docs;
-	sa.dense_q8 = algo == NXSGPU_BM25 ? ix->d_dense_q8 : NULL;
-	sa.dense_q8_stride = ix->dense_q8_stride;
-	sa.blkmap = ix->d_blkmap;
-	sa.bmrank = ix->d_bmrank;
-	sa.bm_words = ix->bm_words;
-	sa.queries = d_q;
-	sa.n_docs = ix->n_docs;
-	sa.qmeta = d_qmeta;
-	sa.items = d_items;
-	sa.k = limit;
-	sa.seg_cap = seg_cap;
-	sa.seg_count = d_seg_count;
-	sa.cand_doc = d_cand_doc;
-	sa.cand_sc = d_cand_sc;
-	sa.overflow = d_ovf;
-	sa.cursors = d_cursors;
-	sa.pub = d_pub;
-	sa.cold_state = d_cold_state;
-	sa.cold_top = d_cold_top;
-	sa.retry_count = d_retry_cnt;
-	sa.retry_items = d_retry_items;
-	sa.pub_sk = d_pub_sk;
-	if (big && nseg && hipMemsetAsync(d_pub_sk, 0, nseg * 32, s_up) != hipSuccess) {
+	scan_args_t sa = make_scan_args(ix, algo, D, limit, seg_cap);
+	if (big && nseg && hipMemsetAsync(D.pub_sk, 0, nseg * 32, s_up) != hipSuccess) {
 		set_error("memset failed");
 		return begin_fail(ix);
 	}
-	memset(&ra, 0, sizeof(ra));
-	ra.flags = ix->cfg.old_replay ? 1u : 0u;
-	ra.qmeta = d_qmeta;
-	ra.seg_cap = seg_cap;
-	ra.seg_count = d_seg_count;
-	ra.cand_doc = d_cand_doc;
-	ra.cand_sc = d_cand_sc;
-	ra.doc_ids = ix->d_doc_ids;
-	ra.k = limit;
+	replay_args_t ra = make_replay_args(ix, D, limit, seg_cap);
 	ra.out_ids = o.d_ids;
 	ra.out_sc = o.d_sc;
 	ra.out_count = o.d_cnt;
-	ra.skip = d_ovf;
 	if (o.records) {
 		ra.rec_base = d_myblock;
-		ra.rec_slot = d_recslot;
+		ra.rec_slot = D.rec_slot;
 		ra.rec_bytes = (uint32_t)sl->rec_bytes;
 	}
 
@@ -1849,7 +1320,7 @@ batch_begin(nxsgpu_index_t *ix, int algo, uint32_t limit, const nxsgpu_query_t *
 	 * the previous batch's scans instead of in front of this batch's.
 	 */
 	if (nq && wl.need_cursors) {
-		launch_cursors(ix, sa, d_bnd_q, (uint32_t)(nseg + nq), s_up);
+		launch_cursors(ix, sa, D.bnd_q, (uint32_t)(nseg + nq), s_up);
 	}
 	tc[1] = now_us();
 	if (s_up != ix->stream && (hipEventRecord(sl->ev_up, s_up) != hipSuccess ||
@@ -1872,11 +1343,12 @@ batch_begin(nxsgpu_index_t *ix, int algo, uint32_t limit, const nxsgpu_query_t *
 			n_l += l.count != 0;
 		}
 		for (launch_t &l : wl.launches) {
-			if ((l.kind == 5 || l.kind == 9) && l.q_count == 0 && l.count && n_l > 2) {
+			if (cls_sparse_dense(l.kind) && l.q_count == 0 && l.count && n_l > 2) {
+				/* (on k_cold + k_scanm<.., DROP> or k_scanb<.., DROP>, CLS_DROP_S included: no retry list) */
 				scan_args_t a = sa;
 				a.item_base = l.first;
-				a.flags |= ix->cfg.drop_prio ? 1u : 0u;
-				a.flags |= (ix->cfg.drop_b && l.nt_bucket <= 5) ? 8u : 0u;
+				a.flags |= ix->cfg.drop_prio ? SCAN_F_PRIO : 0u;
+				a.flags |= (ix->cfg.drop_b && l.nt_bucket <= 5) ? SCAN_F_DROP_B : 0u;
 				a.retry_count = NULL;
 				a.retry_items = NULL;
 				a.retry_cap = 0;
@@ -1911,17 +1383,25 @@ batch_begin(nxsgpu_index_t *ix, int algo, uint32_t limit, const nxsgpu_query_t *
 	if (ix->profiling) (void)hipEventRecord(sl->ev_t[0], ix->stream);
 	sl->n_cls = 0;
 	if (nq) {
+		scan_opts_t so;
+		memset(&so, 0, sizeof(so));
 		if (ix->cfg.one_replay) {
-			launch_scan(big ? MODE_BIG : MODE_TOPK, ix, sa, wl);
+			launch_scan(big ? MODE_BIG : MODE_TOPK, ix, sa, wl, so);
 			if (ix->profiling) (void)hipEventRecord(sl->ev_t[1], ix->stream);
 			nxs_launch_replay(big ? HEAP_LDS : HEAP_REG, nq, big ? (size_t)limit * 8 : 0, ix->stream, ra);
 		} else {
 			/* (profile: "replay" is then only what the last class's replay adds
 			 * after the last scan) */
-			sl->n_cls = 0;
-			launch_scan(big ? MODE_BIG : MODE_TOPK, ix, sa, wl, &ra, d_qorder, ix->profiling ? sl->ev_t[1] : NULL, aside, aside ? s_end : NULL,
-			    ix->profiling ? sl : NULL, sl->ahead ? sl->ev_ahead : NULL,
-			    (!solo && ix->cfg.and_early) ? s_up : NULL, sl->ev_early);
+			so.ra = &ra;
+			so.d_qorder = D.qorder;
+			so.scans_done = ix->profiling ? sl->ev_t[1] : NULL;
+			so.replays_aside = aside;
+			so.replay_stream = aside ? s_end : NULL;
+			so.prof_slot = ix->profiling ? sl : NULL;
+			so.ahead_done = sl->ahead ? sl->ev_ahead : NULL;
+			so.early_stream = (!solo && ix->cfg.and_early) ? s_up : NULL;
+			so.early_done = sl->ev_early;
+			launch_scan(big ? MODE_BIG : MODE_TOPK, ix, sa, wl, so);
 		}
 	} else if (ix->profiling) {
 		(void)hipEventRecord(sl->ev_t[1], ix->stream);
@@ -1933,7 +1413,7 @@ batch_begin(nxsgpu_index_t *ix, int algo, uint32_t limit, const nxsgpu_query_t *
 		return begin_fail(ix);
 	}
 	if (!o.records) {
-		if (hipMemcpyAsync(h_ovf, d_ovf, nq * 4, hipMemcpyDeviceToHost, ix->stream) != hipSuccess ||
+		if (hipMemcpyAsync(H.ovf, D.ovf, nq * 4, hipMemcpyDeviceToHost, ix->stream) != hipSuccess ||
 		    hipEventRecord(sl->ev_done, ix->stream) != hipSuccess) {
 			set_error("copy failed");
 			return begin_fail(ix);

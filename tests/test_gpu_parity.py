@@ -1691,3 +1691,79 @@ def test_full_size_c2_properties(nxs):
         gidx.close()
     finally:
         shutil.rmtree(work, ignore_errors=True)
+
+
+# ---- class routing (which kernel class every query of a batch gets) ------------------------------
+
+ROUTING_ENVS = [{}, {"NXS_GPU_DROP_MINPOST": "1"}, {"NXS_GPU_SCANM_DENS": "1.0", "NXS_GPU_NOSCANB": "1"},
+                {"NXS_GPU_SCANB_DENS": "1.0"}, {"NXS_GPU_BM_GAIN": "0", "NXS_GPU_BM_SHARE": "1073741824"},
+                {"NXS_GPU_SCANS_DROP": "1", "NXS_GPU_DROP_MINPOST": "1"},
+                # (the straggler case: the two dense ORs cannot drop their lists and join the mask-path class)
+                {"NXS_GPU_NODROP": "1"}, {"NXS_GPU_WAVES": "64", "NXS_GPU_MINPOST": "1"},
+                # (many short ranges: top levels sent ahead in launches of their own -- key bit 7)
+                {"NXS_GPU_SCAN1_SPLIT": "1", "NXS_GPU_WAVES": "4096", "NXS_GPU_MINPOST": "64"},
+                {"NXS_GPU_DROP_MINPOST": "1", "NXS_GPU_DROP_NOEARLY": "1", "NXS_GPU_WAVES": "4096", "NXS_GPU_MINPOST": "64"}]
+ROUTING_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "class_routing.json")
+
+
+def routing_env_name(env):
+    return ",".join("%s=%s" % kv for kv in sorted(env.items())) or "default"
+
+
+def routing_queries(terms):
+    """The mixed list of test_every_scan_path_agrees_with_the_oracle, more 5-term queries, 3-term queries of
+    sparse terms and two pure ORs of the five densest terms: above the 64-query cut of a `solo` batch, so the
+    early and side-stream launches exist.  The sparse 3-term ORs are the populated mask-path class that the two
+    dense ORs -- a tile-path class of two, the stragglers -- join when they cannot drop their lists."""
+    rng = random.Random(4)
+    T = lambda r: terms[r - 1].decode()
+    qs = [T(rng.randint(1, 500)) for _ in range(8)]
+    qs += corpus.queries_bool5(terms, 24, seed=6, hi=400)
+    qs += ["%s AND %s" % (T(1), T(2)), "%s AND %s" % (T(3), T(700)), "%s AND %s" % (T(2800), T(1)),
+           "%s AND (%s OR %s)" % (T(900), T(2), T(3)), "%s AND NOT %s" % (T(1), T(2)),
+           "%s OR %s" % (T(2500), T(2900)), "(%s AND %s) OR %s" % (T(1), T(2), T(1500)),
+           "%s AND %s AND %s" % (T(1), T(1200), T(3))]
+    qs += corpus.queries_bool5(terms, 56, seed=6, hi=400)
+    qs += corpus.queries_bool5(terms, 72, seed=8, lo=200, hi=1500, k=3)
+    qs += [" OR ".join(T(r) for r in (1, 2, 3)), " OR ".join(T(r) for r in (3, 4, 5))]
+    return qs
+
+
+def routing_tables(gidx, qs):
+    """{limit: [[key, launches, queries, postings] per class, in launch order]} of one search_batch per limit."""
+    out = {}
+    gidx.set_profiling(True)
+    for limit in (10, 200):
+        gidx.profile(reset=True)
+        gidx.search_batch(qs, limit=limit, fuzzymatch=False)
+        out[str(limit)] = [[c["key"], c["launches"], c["queries"], c["postings"]]
+                           for c in gidx.profile(reset=True)["classes"]]
+    gidx.set_profiling(False)
+    return out
+
+
+@pytest.fixture(scope="module")
+def routing_corpus(tmp_path_factory):
+    return corpus.write_corpus(str(tmp_path_factory.mktemp("routing")), 60_000, 3000, seed=21)
+
+
+@pytest.mark.parametrize("env", ROUTING_ENVS, ids=routing_env_name)
+def test_class_routing_is_pinned(nxs, routing_corpus, monkeypatch, env):
+    """Every query's class, the classes' launch order, the launches sent ahead (key bit 7) and what each
+    launch is charged -- the per-class profile of a 170-query batch at limits 10 and 200 -- equal the tables
+    recorded once, from the library as it was before the scheduler's classes got names, in
+    tests/golden/class_routing.json: routing depends on the corpus, the plans and the switches only, never on
+    timing.  (Recorded with NXS_GPU_NODROP=1 NXS_GPU_NOSTRAGGLER=1 as well, not kept: there the two dense ORs are
+    class 0x113, two queries; in every table here they are inside 0x813.)  (The results themselves: test_every_scan_path_agrees_with_the_oracle.)"""
+    import json
+    for kk, v in env.items():
+        monkeypatch.setenv(kk, v)
+    with open(ROUTING_GOLDEN) as f:
+        want = json.load(f)[routing_env_name(env)]
+    gidx = nxs.open_files(routing_corpus["terms"], routing_corpus["dtmap"])
+    try:
+        got = routing_tables(gidx, routing_queries(corpus.term_strings(3000, seed=21)))
+    finally:
+        gidx.close()
+    for limit in ("10", "200"):
+        assert got[limit] == want[limit], (env, limit)
