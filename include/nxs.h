@@ -46,7 +46,7 @@ typedef enum {
 
 nxs_err_t	nxs_get_error(const nxs_t *, const char **);	/* nxs.h:48 */
 
-/* Parameters (nxs.h:54-67); the query path reads limit / algo / fuzzymatch */
+/* Parameters (nxs.h:54-67); the query path reads limit / algo / fuzzymatch / total */
 struct nxs_params;
 typedef struct nxs_params nxs_params_t;
 
@@ -79,6 +79,28 @@ bool		nxs_resp_iter_result(nxs_resp_t *, nxs_doc_id_t *, float *);
 unsigned	nxs_resp_resultcount(const nxs_resp_t *);
 char *		nxs_resp_tojson(nxs_resp_t *, size_t *);
 void		nxs_resp_release(nxs_resp_t *);
+
+/*
+ * Total match count (new; the reference has no such key).  nxs_resp_resultcount() and the
+ * JSON "count" are the number of results RETURNED, at most `limit` (results.c:196,218).
+ * A search whose params carry "total": true (bool, default false) also counts how many
+ * docs matched: the number of results an unbounded limit would return, i.e. the
+ * cardinality of the expression's doc set (get_expr_bitmap, search.c:118-174) -- 0 under a
+ * ranking function that scores nothing (BM25 on an index with adl < 1, ranking.c:163-166).
+ * It does not depend on the limit or otherwise on the ranking function, leaves out removed
+ * docs, and belongs to the snapshot the batch's results came from.
+ * nxs_resp_total() returns false, *total untouched, if the search did not ask; the JSON
+ * then is what it always was, else it ends ...],"count":N,"total":M}.
+ * Served by nxs_index_search, nxs_index_search_batch[_begin/_end] (any mix of asking and
+ * non-asking batches in flight) and nxs_docshard_search_batch (the shards hold disjoint
+ * docs: the sum of their totals).  REFUSED for now -- the whole batch fails with -1 and
+ * NXS_ERR_INVALID "total is not available on a sharded batch" -- with a communicator
+ * attached, in an emulated world of more than one rank, and by
+ * nxs_docshard_search_batch_rank(): the totals would have to travel in the record and
+ * candidate blocks whose layout all ranks agree on; that is a follow-up.
+ * nxs_index_plan_batch() ignores the key.
+ */
+bool		nxs_resp_total(const nxs_resp_t *, uint64_t *total);
 
 /*
  * Batch entry point (new).  Runs `n` queries with one set of params as one

@@ -369,6 +369,61 @@ int		nxsgpu_batch_begin(nxsgpu_index_t *, int algo, uint32_t limit,
 		    const uint32_t *slot_of_plan, const uint32_t *status,
 		    uint32_t n_slots, int gather);
 int		nxsgpu_batch_end(nxsgpu_index_t *, nxsgpu_batch_view_t *);
+
+/*
+ * ---- total match counts ----------------------------------------------------------
+ *
+ * total of a query = the cardinality of the reference's expression bitmap
+ * (get_expr_bitmap, src/query/search.c:118-174): how many docs the query would
+ * return with an unbounded limit.  It does not depend on the limit or -- apart from
+ * a ranking function that scores nothing (BM25 on an index whose header says
+ * adl < 1: total 0) -- on the ranking function.  The top-k paths skip most matching
+ * docs on purpose, so the count is a pass of its own over the doc ordinals of the
+ * primary CSR (nxs_gpu_count.hip: k_count_tile, k_count_req): no impacts, no heap.
+ *
+ * nxsgpu_count       blocking, totals[n] on the host, fixed-size plans
+ * nxsgpu_count_wide  the same for plans beyond nxsgpu_query_t (k_scanw's count pass)
+ * nxsgpu_search_totals  nxsgpu_search() that also delivers totals[n]: queries that
+ *                    take the exact two-pass path report what its count pass
+ *                    matched, the others are counted by the count kernels
+ * nxsgpu_search_wide_totals  nxsgpu_search_wide() likewise (always the exact path)
+ * nxsgpu_batch_begin_opts  nxsgpu_batch_begin() with options: `totals` queues the
+ *                    count kernels on a stream of the batch, beside its scans;
+ *                    nxsgpu_batch_end_totals() then also hands out totals[n_plans]
+ *                    (plan order; host memory, valid as long as the view's blocks).
+ *                    Not with `gather`: a sharded batch's totals would have to
+ *                    travel in the record blocks every rank agrees on (-1).
+ * NXS_GPU_COUNT=auto|tile|req|scan picks the route: by the query's shape (auto: the
+ * driver kernel where a token is required, else the exact path's count pass),
+ * the tile kernel for everything, the driver kernel wherever a token is required
+ * and the tile kernel for the rest, or the exact path's own count pass (MODE_COUNT)
+ * for everything: the cross-check and baseline.
+ */
+typedef struct {
+	int		totals;		/* count every plan's matches */
+} nxsgpu_batch_opts_t;
+
+int		nxsgpu_count(nxsgpu_index_t *, int algo, const nxsgpu_query_t *queries,
+		    uint32_t n_queries, uint32_t *totals);
+int		nxsgpu_count_wide(nxsgpu_index_t *, int algo, const nxsgpu_wide_query_t *queries,
+		    uint32_t n_queries, uint32_t *totals);
+int		nxsgpu_search_totals(nxsgpu_index_t *, int algo, uint64_t limit,
+		    const nxsgpu_query_t *queries, uint32_t n_queries,
+		    nxsgpu_results_t *res, uint32_t *totals);
+int		nxsgpu_search_wide_totals(nxsgpu_index_t *, int algo, uint64_t limit,
+		    const nxsgpu_wide_query_t *queries, uint32_t n_queries,
+		    nxsgpu_results_t *res, uint32_t *totals);
+int		nxsgpu_batch_begin_opts(nxsgpu_index_t *, int algo, uint32_t limit,
+		    const nxsgpu_query_t *plans, uint32_t n_plans,
+		    const uint32_t *slot_of_plan, const uint32_t *status,
+		    uint32_t n_slots, int gather, const nxsgpu_batch_opts_t *opts);
+int		nxsgpu_batch_end_totals(nxsgpu_index_t *, nxsgpu_batch_view_t *, const uint32_t **totals);
+/* docs per LDS tile of k_count_tile: out[0] with byte masks (<= 8 tokens), out[1] with word masks */
+void		nxsgpu_count_tile_widths(uint32_t out[2]);
+/* profiling (nxsgpu_set_profiling): HIP-event time of the count kernels alone since the last reset --
+ * out[0] / out[1] launches and ms of k_count_tile, out[2] / out[3] of k_count_req, out[4] / out[5] the
+ * queries routed to each */
+void		nxsgpu_count_profile(nxsgpu_index_t *, double out[6], int reset);
 /* number of batches in flight (either API) */
 int		nxsgpu_batches_in_flight(const nxsgpu_index_t *);
 

@@ -12,7 +12,7 @@ the binding (`lib()`).
 import ctypes as C
 import os
 
-__all__ = ["Nxs", "Index", "NxsError", "lib", "build", "LIB_PATH"]
+__all__ = ["Nxs", "Index", "NxsError", "Results", "lib", "build", "LIB_PATH"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
@@ -88,11 +88,11 @@ NXS_H_SYMBOLS = [
     "nxs_index_shard_local", "nxs_index_shard_slice",
     "nxs_index_open_shard", "nxs_docshard_search_batch",
     "nxs_docshard_attach", "nxs_docshard_search_batch_rank",
-    "nxs_docshard_refresh", "nxs_docshard_refresh_rank",
+    "nxs_docshard_refresh", "nxs_docshard_refresh_rank", "nxs_resp_total",
 ]
 # csrc/nxs_hooks.h: test hooks + bench accessors, only in builds with -DNXS_TEST_HOOKS (the default)
 NXS_HOOK_SYMBOLS = ["nxs_index_device", "nxs_index_host_profile", "nxs_index_shard_info", "nxs_test_pool", "nxs_test_assemble",
-                    "nxs_test_fixup_scan", "nxs_test_inject_failure"]
+                    "nxs_test_fixup_scan", "nxs_test_inject_failure", "nxs_test_count_tile_widths"]
 NXS_GPU_H_SYMBOLS = [
     "nxsgpu_device_count", "nxsgpu_last_error", "nxsgpu_index_create",
     "nxsgpu_index_destroy", "nxsgpu_index_df", "nxsgpu_index_postings",
@@ -108,6 +108,8 @@ NXS_GPU_H_SYMBOLS = [
     "nxsgpu_hbm_calibrate",
     "nxsgpu_index_apply", "nxsgpu_index_set_bk", "nxsgpu_index_set_global_df", "nxsgpu_index_impact_passes",
     "nxsgpu_search_candidates", "nxsgpu_merge_candidates",
+    "nxsgpu_count", "nxsgpu_count_wide", "nxsgpu_search_totals", "nxsgpu_search_wide_totals", "nxsgpu_batch_begin_opts",
+    "nxsgpu_batch_end_totals", "nxsgpu_count_tile_widths", "nxsgpu_count_profile",
 ]
 
 _lib = None
@@ -177,6 +179,8 @@ def lib():
     L.nxs_resp_tojson.restype = vp
     L.nxs_resp_tojson.argtypes = [vp, C.POINTER(C.c_size_t)]
     L.nxs_resp_release.argtypes = [vp]
+    L.nxs_resp_total.restype = C.c_bool
+    L.nxs_resp_total.argtypes = [vp, C.POINTER(C.c_uint64)]
     # device shim
     L.nxsgpu_device_count.restype = C.c_int
     L.nxsgpu_last_error.restype = cp
@@ -211,6 +215,10 @@ def lib():
     L.nxsgpu_set_profiling.argtypes = [vp, C.c_int]
     L.nxsgpu_get_profile.argtypes = [vp, C.POINTER(GpuProfile), C.c_int]
     L.nxsgpu_synchronize.argtypes = [vp]
+    L.nxsgpu_count.restype = C.c_int
+    L.nxsgpu_count.argtypes = [vp, C.c_int, C.POINTER(GpuQuery), C.c_uint32, C.POINTER(C.c_uint32)]
+    L.nxsgpu_count_tile_widths.argtypes = [C.POINTER(C.c_uint32)]
+    L.nxsgpu_count_profile.argtypes = [vp, C.POINTER(C.c_double), C.c_int]
     # host-only test hooks
     L.nxs_test_query_repr.restype = vp
     L.nxs_test_query_repr.argtypes = [cp, C.POINTER(vp)]
@@ -291,8 +299,9 @@ class Nxs:
             self._raise()
         return Index(self, h)
 
-    def docshard_search_batch(self, shards, queries, limit=None, algo=None, fuzzymatch=None):
-        """nxs_docshard_search_batch(): one batch over all shards, merged exactly."""
+    def docshard_search_batch(self, shards, queries, limit=None, algo=None, fuzzymatch=None, total=False):
+        """nxs_docshard_search_batch(): one batch over all shards, merged exactly.
+        total: every result list also carries `.total` (the sum of the shards' counts)."""
         L = lib()
         L.nxs_docshard_search_batch.restype = C.c_int
         L.nxs_docshard_search_batch.argtypes = [C.POINTER(C.c_void_p), C.c_uint, C.c_void_p,
@@ -303,7 +312,7 @@ class Nxs:
         qs = (C.c_char_p * max(n, 1))(*[_b(q) for q in queries])
         resps = (C.c_void_p * max(n, 1))()
         errs = (C.c_int * max(n, 1))()
-        p = _make_params(limit, algo, fuzzymatch)
+        p = _make_params(limit, algo, fuzzymatch, total)
         try:
             r = L.nxs_docshard_search_batch(hs, len(shards), p, qs, n, resps, errs)
         finally:
@@ -333,15 +342,16 @@ class Nxs:
                 out.append(NxsError(errs[i], "query %d failed" % i))
         return out
 
-    def docshard_search_batch_rank(self, shard, queries, limit=None, algo=None, fuzzymatch=None):
-        """nxs_docshard_search_batch_rank(): this rank's shard + one all-gather + merge."""
+    def docshard_search_batch_rank(self, shard, queries, limit=None, algo=None, fuzzymatch=None, total=False):
+        """nxs_docshard_search_batch_rank(): this rank's shard + one all-gather + merge.
+        (total: refused for now -- NXS_ERR_INVALID.)"""
         L = lib()
         L.nxs_docshard_search_batch_rank.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_char_p), C.c_size_t,
                                                      C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
         n = len(queries)
         qs = (C.c_char_p * max(n, 1))(*[_b(q) for q in queries])
         resps, errs = (C.c_void_p * max(n, 1))(), (C.c_int * max(n, 1))()
-        p = _make_params(limit, algo, fuzzymatch)
+        p = _make_params(limit, algo, fuzzymatch, total)
         try:
             r = L.nxs_docshard_search_batch_rank(shard._h, p, qs, n, resps, errs)
         finally:
@@ -471,8 +481,14 @@ class Nxs:
         self.close()
 
 
-def _make_params(limit=None, algo=None, fuzzymatch=None):
-    if limit is None and algo is None and fuzzymatch is None:
+class Results(list):
+    """The result list of a search that asked for the total match count: a list like any
+    other, with `.total` = how many docs matched (nxs_resp_total)."""
+    total = None
+
+
+def _make_params(limit=None, algo=None, fuzzymatch=None, total=False):
+    if limit is None and algo is None and fuzzymatch is None and not total:
         return None
     L = lib()
     p = L.nxs_params_create()
@@ -482,6 +498,8 @@ def _make_params(limit=None, algo=None, fuzzymatch=None):
         L.nxs_params_set_str(p, b"algo", _b(algo))
     if fuzzymatch is not None:
         L.nxs_params_set_bool(p, b"fuzzymatch", bool(fuzzymatch))
+    if total:
+        L.nxs_params_set_bool(p, b"total", True)
     return p
 
 
@@ -493,6 +511,10 @@ def _drain(resp):
     while L.nxs_resp_iter_result(resp, C.byref(d), C.byref(s)):
         out.append((d.value, s.value))
     assert len(out) == L.nxs_resp_resultcount(resp)
+    t = C.c_uint64()
+    if L.nxs_resp_total(resp, C.byref(t)):
+        out = Results(out)
+        out.total = t.value
     return out
 
 
@@ -507,9 +529,10 @@ class Index:
     def device(self):
         return lib().nxs_index_device(self._h)
 
-    def search(self, query, limit=None, algo=None, fuzzymatch=None, json=False, params_json=None):
+    def search(self, query, limit=None, algo=None, fuzzymatch=None, json=False, params_json=None, total=False):
         """nxs_index_search(): -> [(doc_id, score), ...] (or the JSON text).
-        params_json: the parameters as the Lua binding passes them (nxs_params_fromjson)."""
+        params_json: the parameters as the Lua binding passes them (nxs_params_fromjson).
+        total: also count the matches -- the list then carries `.total` (the JSON a "total" member)."""
         L = lib()
         if params_json is not None:
             pj = _b(params_json)
@@ -517,7 +540,7 @@ class Index:
             if not p:
                 self.nxs._raise()
         else:
-            p = _make_params(limit, algo, fuzzymatch)
+            p = _make_params(limit, algo, fuzzymatch, total)
         q = _b(query)
         try:
             resp = L.nxs_index_search(self._h, p, q, len(q))
@@ -534,15 +557,15 @@ class Index:
         finally:
             L.nxs_resp_release(resp)
 
-    def search_batch(self, queries, limit=None, algo=None, fuzzymatch=None):
+    def search_batch(self, queries, limit=None, algo=None, fuzzymatch=None, total=False):
         """nxs_index_search_batch(): list of result lists; a failed query
-        yields an NxsError instance in its slot."""
+        yields an NxsError instance in its slot.  total: every list carries `.total`."""
         L = lib()
         n = len(queries)
         qs = (C.c_char_p * n)(*[_b(q) for q in queries])
         resps = (C.c_void_p * n)()
         errs = (C.c_int * n)()
-        p = _make_params(limit, algo, fuzzymatch)
+        p = _make_params(limit, algo, fuzzymatch, total)
         try:
             r = L.nxs_index_search_batch(self._h, p, qs, n, resps, errs)
         finally:
@@ -559,12 +582,13 @@ class Index:
                 out.append(NxsError(errs[i], "query %d failed" % i))
         return out
 
-    def search_batch_begin(self, queries, limit=None, algo=None, fuzzymatch=None):
-        """nxs_index_search_batch_begin(): queue a batch (at most NXS_BATCHES_INFLIGHT = 4 in flight)."""
+    def search_batch_begin(self, queries, limit=None, algo=None, fuzzymatch=None, total=False):
+        """nxs_index_search_batch_begin(): queue a batch (at most NXS_BATCHES_INFLIGHT = 4 in flight).
+        total: the lists search_batch_end() returns for this batch carry `.total`."""
         L = lib()
         n = len(queries)
         qs = (C.c_char_p * max(n, 1))(*[_b(q) for q in queries])
-        p = _make_params(limit, algo, fuzzymatch)
+        p = _make_params(limit, algo, fuzzymatch, total)
         try:
             r = L.nxs_index_search_batch_begin(self._h, p, qs, n)
         finally:
@@ -710,6 +734,13 @@ class Index:
 
     def set_profiling(self, on=True):
         lib().nxsgpu_set_profiling(self.device, 1 if on else 0)
+
+    def count_profile(self, reset=False):
+        """nxsgpu_count_profile(): HIP-event time of the count kernels alone (profiling on)."""
+        out = (C.c_double * 6)()
+        lib().nxsgpu_count_profile(self.device, out, 1 if reset else 0)
+        return {"tile": {"launches": int(out[0]), "ms": out[1], "queries": int(out[4])},
+                "req": {"launches": int(out[2]), "ms": out[3], "queries": int(out[5])}}
 
     def profile(self, reset=False):
         p = GpuProfile()

@@ -1197,6 +1197,8 @@ struct nxs_resp {
 	unsigned	count;
 	unsigned	iter;
 	struct resp_slab *slab;		/* NULL: ids/scores are this response's own */
+	bool		has_total;	/* the search asked for the total match count */
+	uint64_t	total;
 };
 
 typedef struct {
@@ -1237,6 +1239,8 @@ slab_resp(slab_builder_t *b, size_t i, unsigned count)
 	r->count = count;
 	r->iter = 0;
 	r->slab = b->slab;
+	r->has_total = false;
+	r->total = 0;
 	b->used += count;
 	b->slab->refs++;
 	return r;
@@ -1278,6 +1282,16 @@ unsigned
 nxs_resp_resultcount(const nxs_resp_t *r)
 {
 	return r->count;
+}
+
+bool
+nxs_resp_total(const nxs_resp_t *r, uint64_t *total)
+{
+	if (!r->has_total) {
+		return false;
+	}
+	*total = r->total;
+	return true;
 }
 
 /*
@@ -1345,7 +1359,7 @@ fmt_real(char *out, double v)
 char *
 nxs_resp_tojson(nxs_resp_t *r, size_t *len)
 {
-	const size_t cap = 48 + (size_t)r->count * 88;
+	const size_t cap = 80 + (size_t)r->count * 88;
 	char *s = malloc(cap);
 	size_t o = 0;
 
@@ -1359,7 +1373,11 @@ nxs_resp_tojson(nxs_resp_t *r, size_t *len)
 		o += fmt_real(s + o, (double)r->scores[i]);
 		s[o++] = '}';
 	}
-	o += sprintf(s + o, "],\"count\":%u}", r->count);
+	if (r->has_total) {
+		o += sprintf(s + o, "],\"count\":%u,\"total\":%llu}", r->count, (unsigned long long)r->total);
+	} else {
+		o += sprintf(s + o, "],\"count\":%u}", r->count);
+	}
 	if (len) {
 		*len = o;
 	}
@@ -1372,6 +1390,7 @@ typedef struct {
 	uint64_t	limit;
 	int		algo;
 	bool		fuzzymatch;
+	bool		total;		/* "total": also count the matches (nxs_resp_total) */
 } search_params_t;
 
 /* get_search_params: search.c:78-112 */
@@ -1383,6 +1402,7 @@ get_search_params(nxs_index_t *idx, nxs_params_t *params, search_params_t *sp)
 
 	sp->limit = NXS_DEFAULT_RESULTS_LIMIT;
 	sp->fuzzymatch = true;
+	sp->total = false;
 	sp->algo = idx->algo;
 	if (!params) {
 		return 0;
@@ -1399,6 +1419,9 @@ get_search_params(nxs_index_t *idx, nxs_params_t *params, search_params_t *sp)
 	}
 	if (nxs_params_get_bool(params, "fuzzymatch", &fl) == 0 && !fl) {
 		sp->fuzzymatch = false;
+	}
+	if (nxs_params_get_bool(params, "total", &fl) == 0 && fl) {
+		sp->total = true;
 	}
 	return 0;
 }
@@ -2149,9 +2172,10 @@ queue_on_device(nxs_index_t *idx, nxs_pend_t *pd, const search_params_t *sp, boo
 	/* the worker threads are lent for THIS call only (the pool takes one run at a time: the doc-shard
 	 * entry runs a host thread per shard through the same device layer and must never find it set) */
 	nxsgpu_index_set_parallel(idx->dev, api_parallel, nxs);
-	const int brc = nxsgpu_batch_begin(idx->dev, sp->algo, (uint32_t)sp->limit, plans,
+	const nxsgpu_batch_opts_t bo = { .totals = pd->want_total };
+	const int brc = nxsgpu_batch_begin_opts(idx->dev, sp->algo, (uint32_t)sp->limit, plans,
 	    (uint32_t)n_plans, slot_of, status, pd->cap,
-	    idx->comm != NULL && pd->world >= 1 && !idx->emu_world);
+	    idx->comm != NULL && pd->world >= 1 && !idx->emu_world, pd->want_total ? &bo : NULL);
 	nxsgpu_index_set_parallel(idx->dev, NULL, NULL);
 	if (brc != 0) {
 		nxs_decl_err(nxs, NXS_ERR_FATAL, "device search failed: %s", nxsgpu_last_error());
@@ -2279,6 +2303,12 @@ nxs_index_search_batch_begin(nxs_index_t *idx, nxs_params_t *params,
 	if (get_search_params(idx, params, &sp) == -1) {
 		return -1;
 	}
+	/* (totals would have to travel in the record blocks all ranks agree on: a follow-up, include/nxs.h;
+	 * every rank passes the same params, so every rank refuses) */
+	if (sp.total && (idx->comm || idx->emu_world > 1)) {
+		nxs_decl_err(nxs, NXS_ERR_INVALID, "total is not available on a sharded batch");
+		return -1;
+	}
 	for (int i = 0; i < NXSGPU_INFLIGHT; i++) {
 		if (!idx->pend[i].active) {
 			pd = &idx->pend[i];
@@ -2301,6 +2331,7 @@ nxs_index_search_batch_begin(nxs_index_t *idx, nxs_params_t *params,
 	pd->n = n;
 	pd->limit = sp.limit;
 	pd->algo = sp.algo;
+	pd->want_total = sp.total;
 	pd->world = 1;
 	/* query sharding: fixed-size records, limit <= NXSGPU_BIG_K;
 	 * larger limits run replicated -- every rank computes the whole batch */
@@ -2494,12 +2525,20 @@ abort_collective:
 }
 
 /* exact path (nxsgpu_search / nxsgpu_search_wide) for the given local queries */
+/*
+ * tot (or NULL): the total match count of every such query, [nw] -- what the exact path's own count pass
+ * matched.  Fixed-size plans at a limit the candidate filter serves (the re-runs of a record batch's overflowed
+ * queries) are NOT counted again: the batch's count kernels have counted them, tot[j] stays TOT_KEEP.
+ */
+#define	TOT_KEEP	UINT64_MAX
 static int
 run_exact(nxs_index_t *idx, const nxs_pend_t *pd, const uint32_t *which, size_t nw,
-    nxsgpu_results_t *res, nxsgpu_results_t *wres, uint32_t *pos)
+    nxsgpu_results_t *res, nxsgpu_results_t *wres, uint32_t *pos, uint64_t *tot)
 {
 	nxsgpu_query_t *plans = NULL;
 	nxsgpu_wide_query_t *wplans = NULL;
+	uint32_t *t32 = NULL, *w32 = NULL;
+	const bool all_exact = pd->limit > NXSGPU_BIG_K;
 	size_t np = 0, nwd = 0;
 	int ret = -1;
 
@@ -2522,18 +2561,34 @@ run_exact(nxs_index_t *idx, const nxs_pend_t *pd, const uint32_t *which, size_t 
 			plans[np++] = q->plan;
 		}
 	}
-	if (np && nxsgpu_search(idx->dev, pd->algo, pd->limit, plans, (uint32_t)np, res) != 0) {
+	if (tot) {
+		t32 = calloc(np ? np : 1, sizeof(uint32_t));
+		w32 = calloc(nwd ? nwd : 1, sizeof(uint32_t));
+		if (!t32 || !w32) {
+			nxs_decl_err(idx->nxs, NXS_ERR_SYSTEM, "out of memory");
+			goto out;
+		}
+	}
+	if (np && ((tot && all_exact) ?
+	    nxsgpu_search_totals(idx->dev, pd->algo, pd->limit, plans, (uint32_t)np, res, t32) :
+	    nxsgpu_search(idx->dev, pd->algo, pd->limit, plans, (uint32_t)np, res)) != 0) {
 		nxs_decl_err(idx->nxs, NXS_ERR_FATAL, "device search failed: %s", nxsgpu_last_error());
 		goto out;
 	}
-	if (nwd && nxsgpu_search_wide(idx->dev, pd->algo, pd->limit, wplans, (uint32_t)nwd, wres) != 0) {
+	if (nwd && (tot ? nxsgpu_search_wide_totals(idx->dev, pd->algo, pd->limit, wplans, (uint32_t)nwd, wres, w32) :
+	    nxsgpu_search_wide(idx->dev, pd->algo, pd->limit, wplans, (uint32_t)nwd, wres)) != 0) {
 		nxs_decl_err(idx->nxs, NXS_ERR_FATAL, "device search failed: %s", nxsgpu_last_error());
 		goto out;
+	}
+	for (size_t j = 0; tot && j < nw; j++) {
+		tot[j] = (pos[j] & 0x80000000u) ? w32[pos[j] & 0x7fffffffu] : all_exact ? t32[pos[j]] : TOT_KEEP;
 	}
 	ret = 0;
 out:
 	free(plans);
 	free(wplans);
+	free(t32);
+	free(w32);
 	return ret;
 }
 
@@ -2723,6 +2778,7 @@ batch_end_core(nxs_index_t *idx, nxs_pend_t *pd, nxs_resp_t **resps, nxs_err_t *
 	uint8_t *patched = NULL;
 	bool patched_own = true;	/* `patched` is malloc()ed (not the slot's pinned blocks) */
 	uint32_t *which, *pos;
+	uint64_t *tot = NULL, *xtot = NULL;	/* want_total: per local query / per exact re-run */
 	size_t nw = 0, total = 0, n, nl;
 	double t0;
 	const double t_in = now_s();
@@ -2741,13 +2797,19 @@ batch_end_core(nxs_index_t *idx, nxs_pend_t *pd, nxs_resp_t **resps, nxs_err_t *
 	}
 	which = calloc(nl ? nl : 1, sizeof(uint32_t));
 	pos = calloc(nl ? nl : 1, sizeof(uint32_t));
-	if (!which || !pos) {
+	if (pd->want_total) {
+		/* (never sharded: the slice is the whole batch) */
+		tot = calloc(nl ? nl : 1, sizeof(uint64_t));
+		xtot = calloc(nl ? nl : 1, sizeof(uint64_t));
+	}
+	if (!which || !pos || (pd->want_total && (!tot || !xtot))) {
 		nxs_decl_err(nxs, NXS_ERR_SYSTEM, "out of memory");
 		goto out;
 	}
 
 	if (pd->on_device) {
 		nxsgpu_batch_view_t v;
+		const uint32_t *dev_tot = NULL;
 		const uint8_t *blocks;
 		const uint32_t W = (uint32_t)pd->world;
 		/* all W blocks are present after the all-gather; a single rank -- or the
@@ -2756,11 +2818,25 @@ batch_end_core(nxs_index_t *idx, nxs_pend_t *pd, nxs_resp_t **resps, nxs_err_t *
 		bool fixup = false;
 
 		t0 = now_s();
-		if (nxsgpu_batch_end(idx->dev, &v) != 0) {
+		if (nxsgpu_batch_end_totals(idx->dev, &v, &dev_tot) != 0) {
 			nxs_decl_err(nxs, NXS_ERR_FATAL, "device search failed: %s", nxsgpu_last_error());
 			goto out;
 		}
 		idx->hp_wait += now_s() - t0;
+		if (tot) {
+			/* the device's totals are in plan order: the queries queue_on_device sent */
+			size_t j = 0;
+			for (size_t i = 0; i < nl; i++) {
+				const qprep_t *q = &pd->prep[i];
+				if (!q->errcode && !q->wide && !q->empty) {
+					if (!dev_tot) {
+						nxs_decl_err(nxs, NXS_ERR_FATAL, "the batch came back without its totals");
+						goto out;
+					}
+					tot[i] = dev_tot[j++];
+				}
+			}
+		}
 		t0 = now_s();
 		blocks = v.blocks;
 		if (all && v.world != W) {
@@ -2806,7 +2882,7 @@ batch_end_core(nxs_index_t *idx, nxs_pend_t *pd, nxs_resp_t **resps, nxs_err_t *
 			}
 			mine = patched ? patched + (all ? (size_t)pd->rank * v.block_bytes : 0) :
 			    (uint8_t *)(uintptr_t)(blocks + (size_t)pd->rank * v.block_bytes);
-			if (!fix_failed && (run_exact(idx, pd, which, nw, &res, &wres, pos) != 0 ||
+			if (!fix_failed && (run_exact(idx, pd, which, nw, &res, &wres, pos, xtot) != 0 ||
 			    (idx->test_fail_fixup && idx->test_fail_fixup-- == 1 &&
 			    (nxs_decl_err(nxs, NXS_ERR_SYSTEM, "injected failure (test)"), true)))) {
 				if (!(all && W > 1)) {
@@ -2835,6 +2911,9 @@ batch_end_core(nxs_index_t *idx, nxs_pend_t *pd, nxs_resp_t **resps, nxs_err_t *
 				memcpy(rec + 8, rs->doc_ids + rs->offsets[at], (size_t)c * 8);
 				memcpy(rec + 8 + 8 * (size_t)v.k, rs->scores + rs->offsets[at], (size_t)c * 4);
 				st[which[j]] = 0;
+				if (tot && xtot[j] != TOT_KEEP) {
+					tot[which[j]] = xtot[j];	/* (wide plans: k_scanw's count pass; the others were counted with the batch) */
+				}
 			}
 			if (all && W > 1) {
 				uint8_t *gathered = malloc(len);
@@ -2909,13 +2988,16 @@ batch_end_core(nxs_index_t *idx, nxs_pend_t *pd, nxs_resp_t **resps, nxs_err_t *
 				which[nw++] = (uint32_t)i;
 			}
 		}
-		if (run_exact(idx, pd, which, nw, &res, &wres, pos) != 0) {
+		if (run_exact(idx, pd, which, nw, &res, &wres, pos, xtot) != 0) {
 			goto out;
 		}
 		for (size_t j = 0; j < nw; j++) {
 			uint32_t at;
 			const nxsgpu_results_t *rs = exact_pick(&res, &wres, pos[j], &at);
 			total += rs->counts[at];
+			if (tot) {
+				tot[which[j]] = xtot[j];
+			}
 		}
 		if (slab_begin(&sb, n, total) == -1) {
 			nxs_decl_err(nxs, NXS_ERR_SYSTEM, "out of memory");
@@ -2950,11 +3032,19 @@ batch_end_core(nxs_index_t *idx, nxs_pend_t *pd, nxs_resp_t **resps, nxs_err_t *
 			}
 		}
 	}
+	for (size_t i = 0; tot && i < nl; i++) {
+		if (resps[pd->lo + i]) {
+			resps[pd->lo + i]->has_total = true;
+			resps[pd->lo + i]->total = tot[i];	/* (a query that resolves to nothing: 0) */
+		}
+	}
 	if (sb.slab && sb.slab->refs == 0) {
 		free(sb.slab);		/* every query failed */
 	}
 	ret = failed;
 out:
+	free(tot);
+	free(xtot);
 	if (ret == -1 && sb.slab) {
 		for (size_t i = 0; i < n; i++) {
 			resps[i] = NULL;
@@ -3077,6 +3167,7 @@ typedef struct {
 	uint64_t *	ids;	/* [np][cap] */
 	float *		sc;
 	uint32_t *	cnt;	/* [np] */
+	uint32_t *	tot;	/* [np] the shard's total match counts, or NULL */
 	int		ret;
 	char		err[256];
 } ds_job_t;
@@ -3088,6 +3179,9 @@ ds_job_run(void *arg)
 
 	j->ret = nxsgpu_search_candidates(j->shard->dev, j->algo, j->limit, j->plans, j->np, j->cap,
 	    j->ids, j->sc, j->cnt);
+	if (j->ret == 0 && j->tot) {
+		j->ret = nxsgpu_count(j->shard->dev, j->algo, j->plans, j->np, j->tot);
+	}
 	if (j->ret != 0) {
 		snprintf(j->err, sizeof(j->err), "%s", nxsgpu_last_error());
 	}
@@ -3119,7 +3213,7 @@ ds_block_bytes(size_t np, uint32_t cap)
 static int
 docshard_search(nxs_index_t *const *local, unsigned n_local, unsigned n_shards, unsigned my_shard,
     nxs_params_t *params, const char *const *queries, size_t n, nxs_resp_t **resps, nxs_err_t *errs,
-    uint32_t cap0, const uint8_t *gathered, uint8_t **my_block, size_t *my_block_len)
+    uint32_t cap0, const uint8_t *gathered, uint8_t **my_block, size_t *my_block_len, bool rank_form)
 {
 	nxs_index_t *idx0 = local[0];
 	nxs_t *nxs = idx0->nxs;
@@ -3150,6 +3244,11 @@ docshard_search(nxs_index_t *const *local, unsigned n_local, unsigned n_shards, 
 	}
 	if (sp.limit > NXSGPU_BIG_K) {
 		nxs_decl_err(nxs, NXS_ERR_LIMIT, "doc-sharded search takes limit <= %d", NXSGPU_BIG_K);
+		return -1;
+	}
+	/* (the rank form: the totals would have to travel in the candidate blocks; include/nxs.h) */
+	if (sp.total && (rank_form || ranks || gathered || my_block)) {
+		nxs_decl_err(nxs, NXS_ERR_INVALID, "total is not available on a sharded batch");
 		return -1;
 	}
 	for (unsigned s = 0; s < n_local; s++) {
@@ -3217,7 +3316,10 @@ docshard_search(nxs_index_t *const *local, unsigned n_local, unsigned n_shards, 
 			jobs[s].ids = malloc(per * sizeof(uint64_t));
 			jobs[s].sc = malloc(per * sizeof(float));
 			jobs[s].cnt = calloc(np ? np : 1, sizeof(uint32_t));
-			if (!jobs[s].ids || !jobs[s].sc || !jobs[s].cnt) {
+			if (sp.total && !jobs[s].tot) {
+				jobs[s].tot = calloc(np ? np : 1, sizeof(uint32_t));
+			}
+			if (!jobs[s].ids || !jobs[s].sc || !jobs[s].cnt || (sp.total && !jobs[s].tot)) {
 				o_cnt = (free(o_cnt), NULL);
 			}
 			jobs[s].shard = local[s];
@@ -3358,6 +3460,15 @@ docshard_search(nxs_index_t *const *local, unsigned n_local, unsigned n_shards, 
 		memcpy(rp->scores, o_sc + (size_t)plan_of[i] * sp.limit, (size_t)rp->count * sizeof(float));
 		resps[i] = rp;
 	}
+	/* the shards hold disjoint docs: a query's total is the sum of the shards' */
+	for (size_t i = 0; sp.total && i < n; i++) {
+		if (resps[i]) {
+			resps[i]->has_total = true;
+			for (unsigned s = 0; !prep[i].empty && s < n_local; s++) {
+				resps[i]->total += jobs[s].tot[plan_of[i]];
+			}
+		}
+	}
 	if (sb.slab && sb.slab->refs == 0) {
 		free(sb.slab);
 	}
@@ -3367,7 +3478,7 @@ out:
 		nxs_query_release(&prep[i]);
 	}
 	for (unsigned s = 0; jobs && s < n_local; s++) {
-		free(jobs[s].ids); free(jobs[s].sc); free(jobs[s].cnt);
+		free(jobs[s].ids); free(jobs[s].sc); free(jobs[s].cnt); free(jobs[s].tot);
 	}
 	free(jobs); free(thr); free(sendb); free(recvb);
 	free(prep); free(plans); free(plan_of);
@@ -3380,7 +3491,7 @@ int
 nxs_docshard_search_batch(nxs_index_t *const *shards, unsigned n_shards, nxs_params_t *params,
     const char *const *queries, size_t n, nxs_resp_t **resps, nxs_err_t *errs)
 {
-	return docshard_search(shards, n_shards, n_shards, 0, params, queries, n, resps, errs, 0, NULL, NULL, NULL);
+	return docshard_search(shards, n_shards, n_shards, 0, params, queries, n, resps, errs, 0, NULL, NULL, NULL, false);
 }
 
 /*
@@ -3447,7 +3558,7 @@ nxs_docshard_search_batch_rank(nxs_index_t *shard, nxs_params_t *params,
 		nxs_decl_err(shard->nxs, NXS_ERR_INVALID, "no communicator attached (nxs_index_shard)");
 		return -1;
 	}
-	return docshard_search(local, 1, shard->n_shards, shard->shard, params, queries, n, resps, errs, 0, NULL, NULL, NULL);
+	return docshard_search(local, 1, shard->n_shards, shard->shard, params, queries, n, resps, errs, 0, NULL, NULL, NULL, true);
 }
 
 /* ---- N4: following the files (nxs_docshard_refresh[_rank]) ------------------------ */
@@ -3885,7 +3996,7 @@ nxs_test_docshard_block(nxs_index_t *shard, nxs_params_t *params, const char *co
 	*block = NULL;
 	*len = 0;
 	r = docshard_search(local, 1, shard->n_shards, shard->shard, params, queries, n,
-	    resps, NULL, cap, NULL, block, len);
+	    resps, NULL, cap, NULL, block, len, true);
 	free(resps);
 	return r;
 }
@@ -3897,7 +4008,7 @@ nxs_test_docshard_finish(nxs_index_t *shard, nxs_params_t *params, const char *c
 	nxs_index_t *local[1] = { shard };
 
 	return docshard_search(local, 1, shard->n_shards, shard->shard, params, queries, n, resps, errs, cap,
-	    gathered, NULL, NULL);
+	    gathered, NULL, NULL, true);
 }
 
 int
@@ -3950,6 +4061,13 @@ uint64_t
 nxs_test_impact_passes(nxs_index_t *idx)
 {
 	return idx->dev ? nxsgpu_index_impact_passes(idx->dev) : 0;
+}
+
+/* total match counts: docs per LDS tile of k_count_tile (byte masks, word masks) */
+void
+nxs_test_count_tile_widths(uint32_t out[2])
+{
+	nxsgpu_count_tile_widths(out);
 }
 
 #endif /* NXS_TEST_HOOKS */

@@ -117,6 +117,11 @@ cfg_from_env(gpu_cfg_t &c)
 	c.debug_timing = on("NXS_GPU_DEBUG_TIMING");
 	c.down_inline = on("NXS_GPU_DOWN_INLINE");
 	c.old_replay = on("NXS_GPU_OLDREPLAY");
+	{
+		const char *e = getenv("NXS_GPU_COUNT");
+		c.count_mode = !e ? COUNT_AUTO : !strcmp(e, "tile") ? COUNT_TILE : !strcmp(e, "req") ? COUNT_REQ :
+		    !strcmp(e, "scan") ? COUNT_SCAN : COUNT_AUTO;
+	}
 }
 
 /* ------------------------------------------------------------------ */
@@ -624,6 +629,11 @@ nxsgpu_index_destroy(nxsgpu_index_t *ix)
 	if (ix->stream) {
 		(void)hipStreamSynchronize(ix->stream);
 	}
+	if (ix->stream_cnt) {
+		(void)hipStreamSynchronize(ix->stream_cnt);
+		(void)hipStreamDestroy(ix->stream_cnt);
+	}
+	count_buf_free(ix->cnt_blk);
 	(void)hipFree(ix->d_doc_ids);
 	(void)hipFree(ix->d_doc_len);
 	(void)hipFree(ix->d_post_off);
@@ -679,6 +689,9 @@ nxsgpu_index_destroy(nxsgpu_index_t *ix)
 		if (sl.ev_early) (void)hipEventDestroy(sl.ev_early);
 		if (sl.ev_done) (void)hipEventDestroy(sl.ev_done);
 		if (sl.ev_res) (void)hipEventDestroy(sl.ev_res);
+		if (sl.ev_cnt) (void)hipEventDestroy(sl.ev_cnt);
+		if (sl.ev_cnt_up) (void)hipEventDestroy(sl.ev_cnt_up);
+		count_buf_free(sl.cnt);
 		delete_worklist(sl.wl);
 		(void)hipFree(sl.d_blocks);
 		if (sl.h_blocks) {

@@ -24,6 +24,8 @@
  *  nxs_gpu_replay.hip     k_replay: the reference's capped min-heap + heapsort
  *                         (heap.c:58-221; results.c:165-220) replayed exactly
  *  nxs_gpu_wide.hip       k_scanw: queries beyond the fixed-size plan
+ *  nxs_gpu_count.hip      k_count_tile / k_count_req: total match counts from the doc
+ *                         ordinals of the primary CSR (no impacts, no heap)
  *  nxs_gpu_fuzzy.hip      BK-tree search (bktree.c:219-275) + Levenshtein
  *  nxs_gpu_plan.hip       host only: query classes, the work list (build_worklist) and
  *                         the layout of a batch's arrays (batch_layout)
@@ -170,6 +172,22 @@ struct gpu_cfg_t {
 					 * (NOTES.md, round 5) */
 	bool		use_scanb;	/* !NXS_GPU_NOSCANB: the mask path's sparsest queries on the presence-bit kernel (k_scanb) */
 	double		scanb_dens;	/* NXS_GPU_SCANB_DENS: ... those whose lists together hold at most this fraction of the docs */
+	uint32_t	count_mode;	/* NXS_GPU_COUNT=auto|tile|req|scan (COUNT_*): which kernel counts a query's matches */
+};
+enum : uint32_t { COUNT_AUTO = 0, COUNT_TILE = 1, COUNT_REQ = 2, COUNT_SCAN = 3 };
+
+/* a count pass's plan: pinned staging and its device copy, same layout (nxs_gpu_count.hip) */
+struct count_buf_t {
+	void *		d;
+	size_t		d_len;
+	uint8_t *	h;
+	size_t		h_len;
+	size_t		up_len;		/* bytes of the prepared plan */
+	uint32_t	n_q, n_tok, n_prog, n_tot;	/* sizes of the plan's arrays (count_layout) */
+	uint32_t	n_tile, n_req;	/* work items per kernel */
+	uint32_t	q_tile, q_req;	/* queries routed to each */
+	hipEvent_t	ev_k[3];	/* profiling: around k_count_tile and k_count_req (created on demand) */
+	bool		timed;		/* ... recorded for the pass in flight */
 };
 
 void cfg_from_env(gpu_cfg_t &c);
@@ -235,6 +253,11 @@ struct nxsgpu_index {
 		uint32_t *	h_ovf;		/* overflow flags coming back (inside h_stage) */
 		worklist_t *	wl;		/* the slot's work list: its vectors keep their capacity
 						 * (several MB a batch: no mmap / page-fault churn) */
+		/* total match counts (nxsgpu_batch_begin_opts) */
+		count_buf_t	cnt;
+		uint32_t *	h_totals;	/* [nq] in h_stage, or NULL: the batch did not ask */
+		bool		cnt_wait;	/* count kernels are queued on stream_cnt: _end waits for ev_cnt */
+		hipEvent_t	ev_cnt, ev_cnt_up;
 	}		slot[NXSGPU_INFLIGHT];
 	uint64_t	slot_seq;
 
@@ -346,6 +369,12 @@ struct nxsgpu_index {
 	bool		profiling;
 	hipEvent_t	ev[4];
 	nxsgpu_profile_t prof;
+
+	/* total match counts: the stream the count kernels of a pipelined batch run on (created by the first
+	 * batch that asks: the other streams keep their hardware queues), the blocking call's plan buffer */
+	hipStream_t	stream_cnt;
+	count_buf_t	cnt_blk;
+	double		cnt_prof[6];	/* nxsgpu_count_profile */
 };
 
 static inline uint32_t __device__ __host__
@@ -591,6 +620,7 @@ struct batch_dims_t {
 	uint32_t	status_words;	/* record mode: the block's status words, staged on the host */
 	bool		results;	/* out_ids / out_sc [nq][k], out_cnt [nq] */
 	uint32_t	log_cap;	/* candidate log (doc-sharded mode): log_* [nq][log_cap] */
+	bool		totals;		/* total match counts: totals [nq] */
 };
 struct batch_layout_t {
 	/* host -> device, one copy */
@@ -603,6 +633,7 @@ struct batch_layout_t {
 	float *		pub;		/* [nseg], zeroed */
 	uint32_t *	retry_cnt;	/* [RETRY_LISTS], zeroed */
 	uint32_t *	ovf;		/* [nq], zeroed -- and the first array of what comes back */
+	uint32_t *	totals;		/* [nq] what the host knows of each total goes up, the count kernels add the rest */
 	size_t		up_len;
 	uint64_t *	out_ids;
 	float *		out_sc;
@@ -626,6 +657,23 @@ struct batch_layout_t {
 };
 /* base == NULL: offsets and sizes only */
 batch_layout_t	batch_layout(uint8_t *base, const batch_dims_t &d);
+
+/* ---- nxs_gpu_count.hip ---- */
+/* plan the count of `queries` into cb's staging area; h_totals[nq] gets what needs no kernel (0 / -1) */
+/* (own_totals: the totals travel in cb itself -- the blocking call; own_streams: as count_scan_pass, which
+ * takes the queries `auto` routes to the exact path's count pass -- blocking, inside this call) */
+int	count_prepare(nxsgpu_index_t *ix, int algo, const nxsgpu_query_t *queries, uint32_t nq, count_buf_t &cb,
+	    uint32_t *h_totals, bool own_totals, bool own_streams);
+/* the prepared plan up and the kernels on `st`: they ADD to d_totals[nq] (NULL: cb's own); 1, 0: nothing to
+ * launch, -1: error */
+int	count_launch(nxsgpu_index_t *ix, count_buf_t &cb, uint32_t *d_totals, hipStream_t st);
+/* profiling: take the times of a finished pass */
+void	count_collect(nxsgpu_index_t *ix, count_buf_t &cb);
+void	count_buf_free(count_buf_t &cb);
+/* ---- nxs_gpu_search.hip ---- */
+/* NXS_GPU_COUNT=scan: the exact path's count pass (MODE_COUNT) for a whole batch, blocking */
+int	count_scan_pass(nxsgpu_index_t *ix, int algo, const nxsgpu_query_t *queries, uint32_t nq, uint32_t *totals,
+	    bool own_streams);
 
 /* ---- nxs_gpu_comm.hip ---- */
 int	comm_allgather_dev(nxsgpu_comm_t *, const void *send, void *recv, size_t bytes, hipStream_t);

@@ -529,6 +529,7 @@ batch_layout(uint8_t *base, const batch_dims_t &d)
 	L.pub = carve<float>(p, nseg);
 	L.retry_cnt = carve<uint32_t>(p, RETRY_LISTS);
 	L.ovf = carve<uint32_t>(p, nq);
+	L.totals = d.totals ? carve<uint32_t>(p, nq) : NULL;	/* (absent: not even the alignment) */
 	L.up_len = (size_t)(p - base);
 	L.out_ids = carve<uint64_t>(p, d.results ? nq * d.k : 0);
 	L.out_sc = carve<float>(p, d.results ? nq * d.k : 0);

@@ -571,7 +571,7 @@ make_replay_args(const nxsgpu_index_t *ix, const batch_layout_t &L, uint32_t k, 
 
 static int
 search_impl(nxsgpu_index_t *ix, int algo, uint64_t limit, const nxsgpu_query_t *queries,
-    uint32_t nq, nxsgpu_results_t *res, cand_log_t *cl = NULL)
+    uint32_t nq, nxsgpu_results_t *res, cand_log_t *cl = NULL, uint32_t *totals = NULL)
 {
 	/* the candidate filter pass: limits up to NXSGPU_BIG_K (MODE_BIG beyond 64) */
 	const bool fast = limit <= NXSGPU_BIG_K;
@@ -635,6 +635,17 @@ search_impl(nxsgpu_index_t *ix, int algo, uint64_t limit, const nxsgpu_query_t *
 	dims.big = big;
 	dims.results = true;
 	dims.log_cap = cl ? cl->cap : 0;
+	/* total match counts: the candidate filter pass sees only some of a query's matches, so its queries
+	 * are counted by the count kernels, on the same stream (a limit beyond the filter pass: the exact
+	 * path below counts every match itself) */
+	dims.totals = totals != NULL && fast;
+	const bool cnt_scan = dims.totals && ix->cfg.count_mode == COUNT_SCAN;
+	if (cnt_scan && count_scan_pass(ix, algo, queries, nq, totals, false) != 0) {
+		return -1;
+	}
+	if (dims.totals && !cnt_scan && count_prepare(ix, algo, queries, nq, ix->cnt_blk, totals, false, false) != 0) {
+		return -1;
+	}
 	const batch_layout_t sizes = batch_layout(NULL, dims);
 	if (!ensure_ws(ix, sizes.len + 8192) || !ensure_pin(ix, sizes.host_len + 512)) {
 		return -1;
@@ -646,6 +657,9 @@ search_impl(nxsgpu_index_t *ix, int algo, uint64_t limit, const nxsgpu_query_t *
 	memcpy(H.items, wl.items.data(), nseg * sizeof(item_t));
 	memcpy(H.bnd_q, wl.bnd_q.data(), (nseg + nq) * 4);
 	memcpy(H.qorder, wl.qorder.data(), nq * 4);
+	if (dims.totals) {
+		memcpy(H.totals, totals, (size_t)nq * 4);	/* (what the host knows of them) */
+	}
 	if (hipMemcpyAsync(D.q, H.q, D.up_len, hipMemcpyHostToDevice, ix->stream) != hipSuccess) {
 		set_error("query upload failed");
 		return -1;
@@ -691,6 +705,10 @@ search_impl(nxsgpu_index_t *ix, int algo, uint64_t limit, const nxsgpu_query_t *
 			set_error("kernel launch failed");
 			return -1;
 		}
+		if (dims.totals && !cnt_scan && count_launch(ix, ix->cnt_blk, D.totals, ix->stream) < 0) {
+			(void)hipStreamSynchronize(ix->stream);
+			return -1;
+		}
 		if (hipMemcpyAsync(H.ovf, D.ovf, D.down_len, hipMemcpyDeviceToHost, ix->stream) != hipSuccess) {
 			set_error("copy failed");
 			return -1;
@@ -701,6 +719,10 @@ search_impl(nxsgpu_index_t *ix, int algo, uint64_t limit, const nxsgpu_query_t *
 	if (hipStreamSynchronize(ix->stream) != hipSuccess) {
 		set_error("stream sync failed: %s", hipGetErrorString(hipGetLastError()));
 		return -1;
+	}
+	if (dims.totals) {
+		memcpy(totals, H.totals, (size_t)nq * 4);
+		count_collect(ix, ix->cnt_blk);
 	}
 
 	/* host copy of the fast results */
@@ -815,6 +837,9 @@ search_impl(nxsgpu_index_t *ix, int algo, uint64_t limit, const nxsgpu_query_t *
 			const qmeta_t &m = xwl.qmeta[j];
 			const uint64_t matched = sc_off[(uint64_t)m.seg_first + m.n_groups] - sc_off[m.seg_first];
 			const uint64_t hcap = std::min<uint64_t>(limit, matched);
+			if (totals) {
+				totals[xq[j]] = (uint32_t)matched;	/* the exact path sees every match */
+			}
 			hp_off[j + 1] = hp_off[j] + hcap;
 			o_off[j + 1] = o_off[j] + hcap;
 		}
@@ -953,9 +978,30 @@ search_impl(nxsgpu_index_t *ix, int algo, uint64_t limit, const nxsgpu_query_t *
 	return 0;
 }
 
+static int search_blocking(nxsgpu_index_t *, int, uint64_t, const nxsgpu_query_t *, uint32_t, nxsgpu_results_t *, uint32_t *);
+
 extern "C" int
 nxsgpu_search(nxsgpu_index_t *ix, int algo, uint64_t limit, const nxsgpu_query_t *queries,
     uint32_t nq, nxsgpu_results_t *res)
+{
+	return search_blocking(ix, algo, limit, queries, nq, res, NULL);
+}
+
+extern "C" int
+nxsgpu_search_totals(nxsgpu_index_t *ix, int algo, uint64_t limit, const nxsgpu_query_t *queries,
+    uint32_t nq, nxsgpu_results_t *res, uint32_t *totals)
+{
+	if (!totals) {
+		set_error("nxsgpu_search_totals: totals is NULL");
+		return -1;
+	}
+	memset(totals, 0, (size_t)nq * 4);
+	return search_blocking(ix, algo, limit, queries, nq, res, totals);
+}
+
+static int
+search_blocking(nxsgpu_index_t *ix, int algo, uint64_t limit, const nxsgpu_query_t *queries,
+    uint32_t nq, nxsgpu_results_t *res, uint32_t *totals)
 {
 	/* own workspace; with batches in flight, own streams too: a re-run of a few
 	 * overflowed queries must not wait for the next batch's scans (19 ms at C5) */
@@ -965,13 +1011,114 @@ nxsgpu_search(nxsgpu_index_t *ix, int algo, uint64_t limit, const nxsgpu_query_t
 		std::swap(ix->stream2, ix->xstream[1]);
 		std::swap(ix->stream3, ix->xstream[2]);
 	}
-	const int r = search_impl(ix, algo, limit, queries, nq, res);
+	const int r = search_impl(ix, algo, limit, queries, nq, res, NULL, totals);
 	if (busy) {
 		std::swap(ix->stream, ix->xstream[0]);
 		std::swap(ix->stream2, ix->xstream[1]);
 		std::swap(ix->stream3, ix->xstream[2]);
 	}
 	return r;
+}
+
+
+/*
+ * NXS_GPU_COUNT=scan: a batch's totals from pass 1 of the exact two-pass path (MODE_COUNT of the scan
+ * kernels: every match is seen, the count per range is what pass 2 would emit).  Blocking; beside
+ * batches in flight it takes the blocking search's streams.  The cross-check of the count kernels and
+ * the baseline they are measured against.
+ */
+int
+count_scan_pass(nxsgpu_index_t *ix, int algo, const nxsgpu_query_t *queries, uint32_t nq, uint32_t *totals, bool own_streams)
+{
+	/* (own_streams: the caller is not the blocking search, which has swapped its streams in already) */
+	const bool busy = own_streams && nxsgpu_batches_in_flight(ix) != 0;
+	std::vector<dev_query_t> hq(nq);
+	worklist_t wl;
+	uint64_t total_post = 0;
+	int rc = -1;
+
+	memset(totals, 0, (size_t)nq * 4);
+	if (nq == 0) {
+		return 0;
+	}
+	if (ensure_algo(ix, algo) != 0) {
+		return -1;
+	}
+	if (fill_dev_queries(ix, algo, queries, nq, hq.data(), total_post, false) != 0) {
+		return -1;
+	}
+	if (busy) {
+		std::swap(ix->stream, ix->xstream[0]);
+		std::swap(ix->stream2, ix->xstream[1]);
+		std::swap(ix->stream3, ix->xstream[2]);
+	}
+	do {
+		build_worklist(ix, hq.data(), nq, wl, false, 0);
+		const uint64_t nseg = wl.n_segs;
+		std::vector<uint32_t> sc_cnt(nseg);
+		const size_t need = 16384 + nq * sizeof(dev_query_t) + nq * sizeof(qmeta_t) + nseg * sizeof(item_t) + nseg * 8
+		    + nq * 4 + (nseg + nq) * 4 * (1 + NXSGPU_MAX_TOKENS);
+		void *buf = xbuf_get(ix, 0, need);
+		if (!buf) {
+			set_error("hipMalloc(%zu) for the count pass failed", need);
+			break;
+		}
+		uint8_t *mp = (uint8_t *)buf;
+		dev_query_t *d_q = carve<dev_query_t>(mp, nq);
+		qmeta_t *d_qmeta = carve<qmeta_t>(mp, nq);
+		item_t *d_items = carve<item_t>(mp, nseg);
+		uint32_t *d_seg_count = carve<uint32_t>(mp, nseg);
+		float *d_pub = carve<float>(mp, nseg);
+		uint32_t *d_ovf = carve<uint32_t>(mp, nq);
+		uint32_t *d_bnd_q = carve<uint32_t>(mp, nseg + nq);
+		uint32_t *d_cursors = carve<uint32_t>(mp, (nseg + nq) * NXSGPU_MAX_TOKENS);
+		batch_layout_t none;
+		memset(&none, 0, sizeof(none));
+		scan_args_t sa = make_scan_args(ix, algo, none, 0xffffffffu, ix->cfg.seg_cap);
+		sa.queries = d_q;
+		sa.qmeta = d_qmeta;
+		sa.items = d_items;
+		sa.seg_count = d_seg_count;
+		sa.pub = d_pub;
+		sa.overflow = d_ovf;
+		sa.cursors = d_cursors;
+		if (hipMemcpyAsync(d_q, hq.data(), nq * sizeof(dev_query_t), hipMemcpyHostToDevice, ix->stream) != hipSuccess ||
+		    hipMemcpyAsync(d_qmeta, wl.qmeta.data(), nq * sizeof(qmeta_t), hipMemcpyHostToDevice, ix->stream) != hipSuccess ||
+		    hipMemcpyAsync(d_items, wl.items.data(), nseg * sizeof(item_t), hipMemcpyHostToDevice, ix->stream) != hipSuccess ||
+		    hipMemcpyAsync(d_bnd_q, wl.bnd_q.data(), (nseg + nq) * 4, hipMemcpyHostToDevice, ix->stream) != hipSuccess ||
+		    hipMemsetAsync(d_seg_count, 0, (size_t)((uint8_t *)d_bnd_q - (uint8_t *)d_seg_count), ix->stream) != hipSuccess) {
+			set_error("query upload failed");
+		} else {
+			launch_cursors(ix, sa, d_bnd_q, (uint32_t)(nseg + nq));
+			const scan_opts_t scans_only = {};
+			launch_scan(MODE_COUNT, ix, sa, wl, scans_only);
+			if (hipGetLastError() != hipSuccess ||
+			    hipMemcpyAsync(sc_cnt.data(), d_seg_count, nseg * 4, hipMemcpyDeviceToHost, ix->stream) != hipSuccess) {
+				set_error("count pass failed");
+			} else {
+				rc = 0;
+			}
+		}
+		if (hipStreamSynchronize(ix->stream) != hipSuccess) {
+			set_error("count pass failed: %s", hipGetErrorString(hipGetLastError()));
+			rc = -1;
+		}
+		xbuf_put(ix, 0);
+		for (uint32_t j = 0; rc == 0 && j < nq; j++) {
+			const qmeta_t &m = wl.qmeta[j];
+			uint64_t matched = 0;
+			for (uint32_t g = 0; g < m.n_groups; g++) {
+				matched += sc_cnt[(uint64_t)m.seg_first + g];
+			}
+			totals[j] = (uint32_t)matched;
+		}
+	} while (0);
+	if (busy) {
+		std::swap(ix->stream, ix->xstream[0]);
+		std::swap(ix->stream2, ix->xstream[1]);
+		std::swap(ix->stream3, ix->xstream[2]);
+	}
+	return rc;
 }
 
 
@@ -1049,6 +1196,7 @@ struct batch_out_t {
 	const uint32_t *slot_of_plan;
 	const uint32_t *status;
 	uint32_t	n_slots;
+	bool		totals;		/* record batches: count every plan's matches (nxsgpu_batch_begin_opts) */
 };
 
 /* a failed _begin must not leave kernels queued over a slot it reports free */
@@ -1061,6 +1209,9 @@ begin_fail(nxsgpu_index_t *ix)
 	(void)hipStreamSynchronize(ix->stream3);
 	(void)hipStreamSynchronize(ix->stream_rp[1]);
 	(void)hipStreamSynchronize(ix->stream_down);
+	if (ix->stream_cnt) {
+		(void)hipStreamSynchronize(ix->stream_cnt);
+	}
 	(void)hipGetLastError();
 	return -1;
 }
@@ -1125,6 +1276,12 @@ batch_begin(nxsgpu_index_t *ix, int algo, uint32_t limit, const nxsgpu_query_t *
 	sl->world = world;
 	sl->rec_bytes = NXSGPU_REC_BYTES(limit);
 	sl->block_bytes = o.records ? NXSGPU_BLOCK_BYTES(o.n_slots, limit) : 0;
+	sl->h_totals = NULL;
+	sl->cnt_wait = false;
+	if (o.totals && gather) {
+		set_error("total match counts are not available on a sharded batch");
+		return -1;
+	}
 	if (nq == 0 && !o.records) {
 		sl->seq = ++ix->slot_seq;
 		sl->active = true;
@@ -1209,6 +1366,7 @@ batch_begin(nxsgpu_index_t *ix, int algo, uint32_t limit, const nxsgpu_query_t *
 	dims.big = big;
 	dims.rec_slots = o.records;
 	dims.status_words = o.records ? NXSGPU_STATUS_WORDS(o.n_slots) : 0;
+	dims.totals = o.totals && nq;
 	const uint64_t seg_bound = dims.nseg;
 	if (slot_ensure(*sl, 0, batch_layout(NULL, dims).host_len + 32768) != 0) {
 		return -1;
@@ -1244,6 +1402,19 @@ batch_begin(nxsgpu_index_t *ix, int algo, uint32_t limit, const nxsgpu_query_t *
 		memcpy(H.qorder, wl.qorder.data(), nq * 4);
 		memset(H.ovf, 0, nq * 4);
 		memset(H.pub, 0, nseg * 4);
+	}
+	/*
+	 * Total match counts: planned from the caller's plans (build_worklist has put outlier lists in
+	 * place of some of hq's posting ranges); what needs no kernel is in H.totals when it goes up.
+	 * NXS_GPU_COUNT=scan: the exact path's count pass, here and now, on the blocking search's streams.
+	 */
+	const bool cnt_scan = dims.totals && ix->cfg.count_mode == COUNT_SCAN;
+	if (dims.totals) {
+		if (cnt_scan ? count_scan_pass(ix, algo, queries, nq, H.totals, true) != 0 :
+		    count_prepare(ix, algo, queries, nq, sl->cnt, H.totals, false, true) != 0) {
+			return -1;
+		}
+		sl->h_totals = H.totals;
 	}
 	memset(H.retry_cnt, 0, RETRY_LISTS * 4);
 	sl->h_ovf = H.ovf;
@@ -1323,6 +1494,29 @@ batch_begin(nxsgpu_index_t *ix, int algo, uint32_t limit, const nxsgpu_query_t *
 		launch_cursors(ix, sa, D.bnd_q, (uint32_t)(nseg + nq), s_up);
 	}
 	tc[1] = now_us();
+	/* the count kernels wait for the plans' upload (D.totals goes up with them) and nothing else of the batch */
+	const bool cnt_aside = dims.totals && !cnt_scan && !solo && (sl->cnt.n_tile || sl->cnt.n_req);
+	if (cnt_aside) {
+		if ((!ix->stream_cnt && hipStreamCreateWithFlags(&ix->stream_cnt, hipStreamNonBlocking) != hipSuccess) ||
+		    (!sl->ev_cnt && hipEventCreateWithFlags(&sl->ev_cnt, hipEventDisableTiming) != hipSuccess) ||
+		    (!sl->ev_cnt_up && hipEventCreateWithFlags(&sl->ev_cnt_up, hipEventDisableTiming) != hipSuccess) ||
+		    hipEventRecord(sl->ev_cnt_up, s_up) != hipSuccess ||
+		    hipStreamWaitEvent(ix->stream_cnt, sl->ev_cnt_up, 0) != hipSuccess) {
+			set_error("stream for the count kernels: %s", hipGetErrorString(hipGetLastError()));
+			return begin_fail(ix);
+		}
+		/* queued here, in front of the batch's scans: on a stream of their own they run beside them, and the
+		 * totals come back with one copy that _end waits for */
+		if (count_launch(ix, sl->cnt, D.totals, ix->stream_cnt) < 0) {
+			return begin_fail(ix);
+		}
+		if (hipMemcpyAsync(H.totals, D.totals, (size_t)nq * 4, hipMemcpyDeviceToHost, ix->stream_cnt) != hipSuccess ||
+		    hipEventRecord(sl->ev_cnt, ix->stream_cnt) != hipSuccess) {
+			set_error("copy of the totals failed");
+			return begin_fail(ix);
+		}
+		sl->cnt_wait = true;
+	}
 	if (s_up != ix->stream && (hipEventRecord(sl->ev_up, s_up) != hipSuccess ||
 	    hipStreamWaitEvent(ix->stream, sl->ev_up, 0) != hipSuccess)) {
 		set_error("query upload failed");
@@ -1411,6 +1605,16 @@ batch_begin(nxsgpu_index_t *ix, int algo, uint32_t limit, const nxsgpu_query_t *
 	if (hipGetLastError() != hipSuccess) {
 		set_error("kernel launch failed");
 		return begin_fail(ix);
+	}
+	/* a single small batch: the count kernels on the scan stream, like everything else of it */
+	if (dims.totals && !cnt_scan && solo && (sl->cnt.n_tile || sl->cnt.n_req)) {
+		if (count_launch(ix, sl->cnt, D.totals, ix->stream) < 0) {
+			return begin_fail(ix);
+		}
+		if (hipMemcpyAsync(H.totals, D.totals, (size_t)nq * 4, hipMemcpyDeviceToHost, ix->stream) != hipSuccess) {
+			set_error("copy of the totals failed");
+			return begin_fail(ix);
+		}
 	}
 	if (!o.records) {
 		if (hipMemcpyAsync(H.ovf, D.ovf, nq * 4, hipMemcpyDeviceToHost, ix->stream) != hipSuccess ||
@@ -1502,6 +1706,27 @@ nxsgpu_batch_begin(nxsgpu_index_t *ix, int algo, uint32_t limit, const nxsgpu_qu
 	return batch_begin(ix, algo, limit, plans, n_plans, o);
 }
 
+extern "C" int
+nxsgpu_batch_begin_opts(nxsgpu_index_t *ix, int algo, uint32_t limit, const nxsgpu_query_t *plans,
+    uint32_t n_plans, const uint32_t *slot_of_plan, const uint32_t *status, uint32_t n_slots,
+    int gather, const nxsgpu_batch_opts_t *opts)
+{
+	batch_out_t o;
+
+	memset(&o, 0, sizeof(o));
+	if (n_plans && !slot_of_plan) {
+		set_error("nxsgpu_batch_begin: slot_of_plan is NULL");
+		return -1;
+	}
+	o.records = true;
+	o.gather = gather != 0;
+	o.slot_of_plan = slot_of_plan;
+	o.status = status;
+	o.n_slots = n_slots;
+	o.totals = opts && opts->totals;
+	return batch_begin(ix, algo, limit, plans, n_plans, o);
+}
+
 static nxsgpu_index::dev_slot_t *
 oldest_slot(nxsgpu_index_t *ix)
 {
@@ -1518,9 +1743,13 @@ oldest_slot(nxsgpu_index_t *ix)
 static int
 slot_wait(nxsgpu_index_t *ix, nxsgpu_index::dev_slot_t *sl)
 {
-	if (hipEventSynchronize(sl->ev_done) != hipSuccess) {
+	if (hipEventSynchronize(sl->ev_done) != hipSuccess ||
+	    (sl->cnt_wait && hipEventSynchronize(sl->ev_cnt) != hipSuccess)) {
 		set_error("batch failed: %s", hipGetErrorString(hipGetLastError()));
 		return -1;
+	}
+	if (sl->h_totals) {
+		count_collect(ix, sl->cnt);
 	}
 	if (ix->profiling && (sl->nq || sl->records)) {
 		float a = 0, b = 0;
@@ -1588,8 +1817,17 @@ nxsgpu_search_dev_end(nxsgpu_index_t *ix)
 extern "C" int
 nxsgpu_batch_end(nxsgpu_index_t *ix, nxsgpu_batch_view_t *view)
 {
+	return nxsgpu_batch_end_totals(ix, view, NULL);
+}
+
+extern "C" int
+nxsgpu_batch_end_totals(nxsgpu_index_t *ix, nxsgpu_batch_view_t *view, const uint32_t **totals)
+{
 	nxsgpu_index::dev_slot_t *sl = oldest_slot(ix);
 
+	if (totals) {
+		*totals = NULL;
+	}
 	if (!sl) {
 		set_error("nxsgpu_batch_end: no batch in flight");
 		return -1;
@@ -1609,6 +1847,9 @@ nxsgpu_batch_end(nxsgpu_index_t *ix, nxsgpu_batch_view_t *view)
 	view->block_bytes = sl->block_bytes;
 	/* with one rank the own block sits at position 0 of both copies */
 	view->blocks = sl->h_blocks;
+	if (totals) {
+		*totals = sl->h_totals;		/* (in the slot's staging area: untouched until the slot's next batch) */
+	}
 	return 0;
 }
 

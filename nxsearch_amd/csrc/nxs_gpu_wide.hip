@@ -209,9 +209,10 @@ k_scanw(const wide_args_t A)
 
 /* ------------------------------------------------------------------ */
 
-extern "C" int
-nxsgpu_search_wide(nxsgpu_index_t *ix, int algo, uint64_t limit, const nxsgpu_wide_query_t *queries,
-    uint32_t nq, nxsgpu_results_t *res)
+/* res == NULL: the count pass only (nxsgpu_count_wide); totals (or NULL): what it matched per query */
+static int
+wide_impl(nxsgpu_index_t *ix, int algo, uint64_t limit, const nxsgpu_wide_query_t *queries,
+    uint32_t nq, nxsgpu_results_t *res, uint32_t *totals)
 {
 	const bool valid = (algo == NXSGPU_BM25) ? ix->bm25_valid : ix->tfidf_valid;
 	std::vector<wide_dev_t> hq(nq);
@@ -223,8 +224,10 @@ nxsgpu_search_wide(nxsgpu_index_t *ix, int algo, uint64_t limit, const nxsgpu_wi
 	void *ws = NULL, *ws2 = NULL;
 	int rc = -1;
 
-	memset(res, 0, sizeof(*res));
-	res->n_queries = nq;
+	if (res) {
+		memset(res, 0, sizeof(*res));
+		res->n_queries = nq;
+	}
 	if (algo != NXSGPU_BM25 && algo != NXSGPU_TF_IDF) {
 		set_error("invalid algorithm");
 		return -1;
@@ -359,6 +362,13 @@ nxsgpu_search_wide(nxsgpu_index_t *ix, int algo, uint64_t limit, const nxsgpu_wi
 		for (uint32_t j = 0; j < nq; j++) {
 			const uint64_t matched = sc_off[(size_t)qmeta[j].seg_first + qmeta[j].n_groups] - sc_off[qmeta[j].seg_first];
 			hp_off[j + 1] = hp_off[j] + std::min<uint64_t>(limit, matched);
+			if (totals) {
+				totals[j] = (uint32_t)matched;
+			}
+		}
+		if (!res) {
+			rc = 0;
+			break;
 		}
 		const uint64_t tot_c = sc_off[nseg], tot_o = hp_off[nq];
 		const size_t need2 = 8192 + ((size_t)nseg + 1) * 8 + tot_c * 8 + tot_o * 8 + tot_o * 12 + ((size_t)nq + 1) * 8 + nq * 4;
@@ -424,6 +434,9 @@ nxsgpu_search_wide(nxsgpu_index_t *ix, int algo, uint64_t limit, const nxsgpu_wi
 	if (rc != 0) {
 		return -1;
 	}
+	if (!res) {
+		return 0;
+	}
 	res->counts = (uint32_t *)calloc(nq, sizeof(uint32_t));
 	res->offsets = (uint64_t *)calloc((size_t)nq + 1, sizeof(uint64_t));
 	for (uint32_t i = 0; i < nq; i++) {
@@ -439,4 +452,36 @@ nxsgpu_search_wide(nxsgpu_index_t *ix, int algo, uint64_t limit, const nxsgpu_wi
 	}
 	res->exact_requeries = nq;
 	return 0;
+}
+
+extern "C" int
+nxsgpu_search_wide(nxsgpu_index_t *ix, int algo, uint64_t limit, const nxsgpu_wide_query_t *queries,
+    uint32_t nq, nxsgpu_results_t *res)
+{
+	return wide_impl(ix, algo, limit, queries, nq, res, NULL);
+}
+
+/* ... with what its count pass matched per query (pass 1 of the two: no further device work) */
+extern "C" int
+nxsgpu_search_wide_totals(nxsgpu_index_t *ix, int algo, uint64_t limit, const nxsgpu_wide_query_t *queries,
+    uint32_t nq, nxsgpu_results_t *res, uint32_t *totals)
+{
+	if (!totals) {
+		set_error("nxsgpu_search_wide_totals: totals is NULL");
+		return -1;
+	}
+	memset(totals, 0, (size_t)nq * 4);
+	return wide_impl(ix, algo, limit, queries, nq, res, totals);
+}
+
+/* total match counts of wide queries: k_scanw's count pass (they are rare and always exact) */
+extern "C" int
+nxsgpu_count_wide(nxsgpu_index_t *ix, int algo, const nxsgpu_wide_query_t *queries, uint32_t nq, uint32_t *totals)
+{
+	if (!totals) {
+		set_error("nxsgpu_count_wide: totals is NULL");
+		return -1;
+	}
+	memset(totals, 0, (size_t)nq * 4);
+	return wide_impl(ix, algo, 1, queries, nq, NULL, totals);
 }

@@ -69,6 +69,9 @@ uint32_t	nxs_test_docshard_refresh_finish(nxs_index_t *shard, const uint8_t *gat
 int		nxs_test_docshard_refresh_settle(nxs_index_t *shard, const uint32_t *fin, unsigned W);
 int		nxs_test_docshard_agree(const uint64_t *recs, unsigned W, const uint64_t consumed[4], uint64_t out[8]);
 uint64_t	nxs_test_impact_passes(nxs_index_t *);
+/* total match counts: docs per LDS tile of k_count_tile -- out[0] byte masks (<= 8 tokens), out[1] word masks
+ * (tests straddle them) */
+void		nxs_test_count_tile_widths(uint32_t out[2]);
 
 #endif /* NXS_TEST_HOOKS */
 #endif /* NXS_HOOKS_H */

@@ -82,6 +82,7 @@ typedef struct nxs_delta nxs_delta_t;
 typedef struct nxs_pend {
 	bool		active;
 	bool		on_device;	/* queued through nxsgpu_batch_begin */
+	bool		want_total;	/* params "total": count every query's matches */
 	size_t		n;		/* queries of the whole batch */
 	size_t		lo, hi;		/* this rank's slice */
 	uint32_t	cap;		/* record slots per rank */
