@@ -46,7 +46,8 @@ typedef enum {
 
 nxs_err_t	nxs_get_error(const nxs_t *, const char **);	/* nxs.h:48 */
 
-/* Parameters (nxs.h:54-67); the query path reads limit / algo / fuzzymatch / total */
+/* Parameters (nxs.h:54-67); the query path reads limit / algo / fuzzymatch / total,
+ * nxs_index_suggest reads suggest_limit / suggest_maxdist */
 struct nxs_params;
 typedef struct nxs_params nxs_params_t;
 
@@ -101,6 +102,62 @@ void		nxs_resp_release(nxs_resp_t *);
  * nxs_index_plan_batch() ignores the key.
  */
 bool		nxs_resp_total(const nxs_resp_t *, uint64_t *total);
+
+/*
+ * Spelling suggestions (new; the reference has no "did you mean" call).  For one raw token -- not a
+ * query: the string goes through the index's filters as a query token does (normalizer / lowercase,
+ * stop words, stemmer) and is then compared as it stands -- the ELIGIBLE terms are the dictionary
+ * terms that
+ *   - have a posting in a live doc of the current snapshot (df > 0: a term whose docs were all removed
+ *     is not suggested, whatever its on-disk total says), and
+ *   - lie within byte-wise Levenshtein distance "suggest_maxdist" (uint, 1 or 2, default 2) of the
+ *     token (levdist, src/algo/levdist.c:67-150).
+ * The result is the first min(k, matches) of them, k = "suggest_limit" (uint, 1..NXS_SUGGEST_MAX,
+ * default 5), in the order distance ascending, df descending, term id ascending -- each with its
+ * bytes, distance and df -- and `matches`, the exact number of eligible terms.  A value out of range
+ * fails the call with NXS_ERR_INVALID and a message that names the key.  An exact hit (distance 0) is
+ * eligible and comes first.  On an index with the stemmer filter the token is stemmed and the
+ * suggestions are STEMS, as the dictionary holds them.  A string the filters drop (a stop word)
+ * yields an empty list, matches 0 and nxs_sugg_dropped() true: not an error.
+ *
+ * This is not the set "fuzzymatch" draws from: that search takes the first term the BK-tree walk
+ * reaches (bktree.c:219-275, idxterm.c:238-242) -- one member of the set, not the nearest and not
+ * the most frequent -- never enters the subtree below a distance-63 child and goes by the on-disk
+ * totals.  The term a fuzzy search resolves a token to is in the list whenever it has df > 0 and
+ * matches <= k.
+ *
+ * The call re-syncs with the files as nxs_index_search does and is allowed while batches are in
+ * flight (nxs_index_search_batch_begin), a batch whose fuzzy pass is still pending included: it
+ * runs on a stream and workspace of its own and neither finishes nor reorders them -- unless the
+ * files have moved, which finishes them first as any _begin would (their responses wait for _end).
+ * It is local: with a communicator attached (nxs_index_shard) every rank answers its own calls, no
+ * collective, and while batches are in flight from the snapshot they run on.  On a handle from
+ * nxs_index_open_shard it fails with NXS_ERR_INVALID "suggest is not available on a doc shard" (a
+ * shard's dictionary and df are collection-wide, its postings are not: a follow-up).
+ *
+ * nxs_index_suggest_batch: out[i] receives an object or NULL if token i failed (errs[i], may be
+ * NULL); returns the number of failed tokens, or -1 if the batch could not run (nxs_get_error).
+ * nxs_sugg_get: false if i >= nxs_sugg_count(); *term is owned by the object, NUL-terminated (any of
+ * the out pointers may be NULL).  nxs_sugg_tojson (the caller frees, like nxs_resp_tojson):
+ *   {"token":"<filtered token>","suggestions":[{"term":"...","distance":1,"df":12},...],"matches":7}
+ * strings pass UTF-8 through; a double quote, a backslash and every byte below 0x20 (the last as a
+ * six-character escape: backslash, u, 00 and two hex digits) are escaped.
+ */
+#define	NXS_SUGGEST_MAX		32
+struct nxs_sugg;
+typedef struct nxs_sugg nxs_sugg_t;
+
+nxs_sugg_t *	nxs_index_suggest(nxs_index_t *, nxs_params_t *, const char *token, size_t len);
+int		nxs_index_suggest_batch(nxs_index_t *, nxs_params_t *,
+		    const char *const *tokens, size_t n,
+		    nxs_sugg_t **out, nxs_err_t *errs);
+unsigned	nxs_sugg_count(const nxs_sugg_t *);
+uint64_t	nxs_sugg_matches(const nxs_sugg_t *);
+bool		nxs_sugg_dropped(const nxs_sugg_t *);
+bool		nxs_sugg_get(const nxs_sugg_t *, unsigned i, const char **term, size_t *len,
+		    unsigned *distance, uint64_t *df);
+char *		nxs_sugg_tojson(nxs_sugg_t *, size_t *);
+void		nxs_sugg_release(nxs_sugg_t *);
 
 /*
  * Batch entry point (new).  Runs `n` queries with one set of params as one

@@ -20,6 +20,8 @@
  *                           = bktree_search (src/algo/bktree.c:219-275) with
  *                           the bktree_distfunc_t seam bound to levdist
  *                           (src/algo/levdist.c:67-150).
+ *   nxsgpu_suggest       (new: no seam in the reference) every term near a
+ *                           token, ranked -- the same screen and distance.
  */
 #ifndef NXS_GPU_H
 #define NXS_GPU_H
@@ -286,6 +288,37 @@ int		nxsgpu_fuzzy_begin(nxsgpu_index_t *, const uint8_t *tok_bytes,
 		    const uint32_t *tok_off, uint32_t n_tokens);
 int		nxsgpu_fuzzy_end(nxsgpu_index_t *, int slot, const uint8_t *tok_bytes,
 		    const uint32_t *tok_off, uint32_t n_tokens, uint32_t *term_ids);
+
+/*
+ * ---- spelling suggestions ----------------------------------------------------------
+ *
+ * nxsgpu_suggest: for each of n_tokens raw tokens (bytes tok_off[i] .. tok_off[i + 1], already through the
+ * index's filters) the ELIGIBLE terms -- a posting in a live doc (df > 0, what nxsgpu_index_df reports) and
+ * byte-wise Levenshtein distance <= maxdist (1 or 2) -- in the order distance ascending, df descending, term
+ * id ascending.  Rows of k (1..32) entries: term_ids / dist / df [n_tokens][k], counts[i] = min(k, matches[i])
+ * entries of row i are valid, matches[i] is the exact number of eligible terms.  This is not the set the
+ * BK walk of nxsgpu_fuzzy visits: terms below a slot-63 child count, terms whose docs are all removed do
+ * not, and an exact hit comes first.
+ *
+ * The pass shares the match-first search's screen (k_fz_filter) over a candidate permutation of its own,
+ * built by the first call and rebuilt after nxsgpu_index_apply / _set_bk / _set_global_df (a generation
+ * counter: an index that is never asked builds, uploads and launches nothing).  It runs on a stream and
+ * workspace of its own: allowed while batches and fuzzy passes (nxsgpu_fuzzy_begin) are in flight, takes
+ * none of their slots.  A queue that overflows (NXS_GPU_FUZZY_CAND bounds the survivor queues) repeats the
+ * pass with fewer tokens, down to one token with queues of 8 bytes x candidates: answers never change.
+ * Tokens of more than 64 bytes, and every token under NXS_GPU_SUGGEST=host (the cross-check route), are
+ * ranked on the host over a copy of the BK image.  0 / -1.
+ *
+ * nxsgpu_suggest_profile (nxsgpu_set_profiling): since the last reset -- out[0] device passes, out[1] their
+ * HIP-event ms, out[2] k_bk_peq + k_fz_filter, out[3] k_sg_dist, out[4] k_sg_scan + k_sg_scatter, out[5]
+ * k_sg_select, out[6] survivors of the screen, out[7] matches, out[8] tokens ranked on the host (counted
+ * always), out[9] passes repeated after an overflow (counted always).
+ */
+#define	NXSGPU_SUGGEST_PROF	10
+int		nxsgpu_suggest(nxsgpu_index_t *, const uint8_t *tok_bytes, const uint32_t *tok_off,
+		    uint32_t n_tokens, uint32_t maxdist, uint32_t k,
+		    uint32_t *term_ids, uint8_t *dist, uint32_t *df, uint32_t *counts, uint32_t *matches);
+void		nxsgpu_suggest_profile(nxsgpu_index_t *, double out[NXSGPU_SUGGEST_PROF], int reset);
 
 /*
  * ---- host batches as fixed-size records; query sharding over several GPUs ----

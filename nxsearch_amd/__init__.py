@@ -12,7 +12,7 @@ the binding (`lib()`).
 import ctypes as C
 import os
 
-__all__ = ["Nxs", "Index", "NxsError", "Results", "lib", "build", "LIB_PATH"]
+__all__ = ["Nxs", "Index", "NxsError", "Results", "Suggestions", "lib", "build", "LIB_PATH"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
@@ -89,10 +89,13 @@ NXS_H_SYMBOLS = [
     "nxs_index_open_shard", "nxs_docshard_search_batch",
     "nxs_docshard_attach", "nxs_docshard_search_batch_rank",
     "nxs_docshard_refresh", "nxs_docshard_refresh_rank", "nxs_resp_total",
+    "nxs_index_suggest", "nxs_index_suggest_batch", "nxs_sugg_count", "nxs_sugg_matches", "nxs_sugg_dropped",
+    "nxs_sugg_get", "nxs_sugg_tojson", "nxs_sugg_release",
 ]
 # csrc/nxs_hooks.h: test hooks + bench accessors, only in builds with -DNXS_TEST_HOOKS (the default)
 NXS_HOOK_SYMBOLS = ["nxs_index_device", "nxs_index_host_profile", "nxs_index_shard_info", "nxs_test_pool", "nxs_test_assemble",
-                    "nxs_test_fixup_scan", "nxs_test_inject_failure", "nxs_test_count_tile_widths"]
+                    "nxs_test_fixup_scan", "nxs_test_inject_failure", "nxs_test_count_tile_widths",
+                    "nxs_test_suggest_host", "nxs_test_suggest_params", "nxs_test_sugg_build"]
 NXS_GPU_H_SYMBOLS = [
     "nxsgpu_device_count", "nxsgpu_last_error", "nxsgpu_index_create",
     "nxsgpu_index_destroy", "nxsgpu_index_df", "nxsgpu_index_postings",
@@ -110,6 +113,7 @@ NXS_GPU_H_SYMBOLS = [
     "nxsgpu_search_candidates", "nxsgpu_merge_candidates",
     "nxsgpu_count", "nxsgpu_count_wide", "nxsgpu_search_totals", "nxsgpu_search_wide_totals", "nxsgpu_batch_begin_opts",
     "nxsgpu_batch_end_totals", "nxsgpu_count_tile_widths", "nxsgpu_count_profile",
+    "nxsgpu_suggest", "nxsgpu_suggest_profile",
 ]
 
 _lib = None
@@ -181,6 +185,22 @@ def lib():
     L.nxs_resp_release.argtypes = [vp]
     L.nxs_resp_total.restype = C.c_bool
     L.nxs_resp_total.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.nxs_index_suggest.restype = vp
+    L.nxs_index_suggest.argtypes = [vp, vp, cp, C.c_size_t]
+    L.nxs_index_suggest_batch.restype = C.c_int
+    L.nxs_index_suggest_batch.argtypes = [vp, vp, C.POINTER(cp), C.c_size_t, C.POINTER(vp), C.POINTER(C.c_int)]
+    L.nxs_sugg_count.restype = C.c_uint
+    L.nxs_sugg_count.argtypes = [vp]
+    L.nxs_sugg_matches.restype = C.c_uint64
+    L.nxs_sugg_matches.argtypes = [vp]
+    L.nxs_sugg_dropped.restype = C.c_bool
+    L.nxs_sugg_dropped.argtypes = [vp]
+    L.nxs_sugg_get.restype = C.c_bool
+    L.nxs_sugg_get.argtypes = [vp, C.c_uint, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_uint),
+                               C.POINTER(C.c_uint64)]
+    L.nxs_sugg_tojson.restype = vp
+    L.nxs_sugg_tojson.argtypes = [vp, C.POINTER(C.c_size_t)]
+    L.nxs_sugg_release.argtypes = [vp]
     # device shim
     L.nxsgpu_device_count.restype = C.c_int
     L.nxsgpu_last_error.restype = cp
@@ -219,6 +239,11 @@ def lib():
     L.nxsgpu_count.argtypes = [vp, C.c_int, C.POINTER(GpuQuery), C.c_uint32, C.POINTER(C.c_uint32)]
     L.nxsgpu_count_tile_widths.argtypes = [C.POINTER(C.c_uint32)]
     L.nxsgpu_count_profile.argtypes = [vp, C.POINTER(C.c_double), C.c_int]
+    L.nxsgpu_suggest.restype = C.c_int
+    L.nxsgpu_suggest.argtypes = [vp, cp, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32,
+                                 C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32),
+                                 C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.nxsgpu_suggest_profile.argtypes = [vp, C.POINTER(C.c_double), C.c_int]
     # host-only test hooks
     L.nxs_test_query_repr.restype = vp
     L.nxs_test_query_repr.argtypes = [cp, C.POINTER(vp)]
@@ -487,6 +512,47 @@ class Results(list):
     total = None
 
 
+class Suggestions(list):
+    """The suggestions for one token (nxs_sugg_t): [(term: bytes, distance, df), ...] best first, with
+    `.matches` = the exact number of eligible terms and `.dropped` = the filters dropped the token (a stop
+    word)."""
+    matches = 0
+    dropped = False
+
+
+def _drain_sugg(sg, json=False):
+    """nxs_sugg_t -> Suggestions (or its JSON text); releases the object"""
+    L = lib()
+    try:
+        if json:
+            n = C.c_size_t()
+            return _take(L.nxs_sugg_tojson(sg, C.byref(n)))
+        out = Suggestions()
+        term, ln, d, df = C.c_void_p(), C.c_size_t(), C.c_uint(), C.c_uint64()
+        i = 0
+        while L.nxs_sugg_get(sg, i, C.byref(term), C.byref(ln), C.byref(d), C.byref(df)):
+            out.append((C.string_at(term.value, ln.value), d.value, df.value))
+            i += 1
+        assert i == L.nxs_sugg_count(sg)
+        out.matches = L.nxs_sugg_matches(sg)
+        out.dropped = bool(L.nxs_sugg_dropped(sg))
+        return out
+    finally:
+        L.nxs_sugg_release(sg)
+
+
+def _suggest_params(limit=None, maxdist=None):
+    if limit is None and maxdist is None:
+        return None
+    L = lib()
+    p = L.nxs_params_create()
+    if limit is not None:
+        L.nxs_params_set_uint(p, b"suggest_limit", limit)
+    if maxdist is not None:
+        L.nxs_params_set_uint(p, b"suggest_maxdist", maxdist)
+    return p
+
+
 def _make_params(limit=None, algo=None, fuzzymatch=None, total=False):
     if limit is None and algo is None and fuzzymatch is None and not total:
         return None
@@ -725,6 +791,35 @@ class Index:
         if want_visited:
             return list(ids[:n]), list(vis[:n])
         return list(ids[:n])
+
+    def suggest(self, tokens, limit=None, maxdist=None, json=False):
+        """nxs_index_suggest_batch(): for every raw token (not a query; it goes through the index's filters)
+        the dictionary terms within `maxdist` (1 or 2, default 2) that some live doc holds, best `limit`
+        (1..32, default 5) by distance, then df descending, then term id -> a list of Suggestions, one per
+        token (an NxsError instance in the slot of a token that failed); json: their JSON texts."""
+        L = lib()
+        n = len(tokens)
+        ts = (C.c_char_p * max(n, 1))(*[_b(t) for t in tokens])
+        out = (C.c_void_p * max(n, 1))()
+        errs = (C.c_int * max(n, 1))()
+        p = _suggest_params(limit, maxdist)
+        try:
+            r = L.nxs_index_suggest_batch(self._h, p, ts, n, out, errs)
+        finally:
+            if p:
+                L.nxs_params_release(p)
+        if r < 0:
+            self.nxs._raise()
+        return [_drain_sugg(out[i], json) if out[i] else NxsError(errs[i], "token %d failed" % i) for i in range(n)]
+
+    def suggest_profile(self, reset=False):
+        """nxsgpu_suggest_profile(): HIP-event times of the suggest pass per kernel (profiling on), its queue
+        counts, tokens ranked on the host and passes repeated after a queue overflow."""
+        out = (C.c_double * 10)()
+        lib().nxsgpu_suggest_profile(self.device, out, 1 if reset else 0)
+        return {"passes": int(out[0]), "ms": out[1], "screen_ms": out[2], "dist_ms": out[3], "group_ms": out[4],
+                "select_ms": out[5], "survivors": int(out[6]), "matches": int(out[7]), "host_tokens": int(out[8]),
+                "overflow_reruns": int(out[9])}
 
     def set_plan_cache(self, on=True):
         """bench: the index's plan cache (query string -> compiled plan) on / off."""

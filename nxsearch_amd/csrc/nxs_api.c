@@ -27,6 +27,7 @@
 
 #include "nxs_impl.h"
 #include "nxs_hooks.h"
+#include "nxs_suggest.h"
 
 struct plan_cache;
 static void plan_cache_destroy(struct plan_cache *);
@@ -3109,6 +3110,408 @@ nxs_index_search(nxs_index_t *idx, nxs_params_t *params, const char *query, size
 	}
 	return resp;
 }
+
+/* ---- spelling suggestions (nxs_index_suggest) ---------------------------------------- */
+
+typedef struct {
+	char *		term;		/* owned by the object, NUL-terminated */
+	size_t		len;
+	unsigned	dist;
+	uint64_t	df;
+} sugg_item_t;
+
+struct nxs_sugg {
+	char *		token;		/* the token after the filters (empty when dropped) */
+	size_t		token_len;
+	bool		dropped;
+	uint64_t	matches;
+	unsigned	count;
+	sugg_item_t	items[];
+};
+
+/* one block: the object, its items, the strings */
+static nxs_sugg_t *
+sugg_build(const char *token, size_t token_len, bool dropped, uint64_t matches, unsigned count,
+    const uint8_t *const *terms, const size_t *lens, const unsigned *dists, const uint64_t *dfs)
+{
+	size_t bytes = sizeof(nxs_sugg_t) + count * sizeof(sugg_item_t) + token_len + 1;
+	nxs_sugg_t *sg;
+	char *str;
+
+	for (unsigned i = 0; i < count; i++) {
+		bytes += lens[i] + 1;
+	}
+	if ((sg = malloc(bytes)) == NULL) {
+		return NULL;
+	}
+	str = (char *)&sg->items[count];
+	sg->token = str;
+	sg->token_len = token_len;
+	memcpy(str, token, token_len);
+	str[token_len] = '\0';
+	str += token_len + 1;
+	sg->dropped = dropped;
+	sg->matches = matches;
+	sg->count = count;
+	for (unsigned i = 0; i < count; i++) {
+		sg->items[i].term = str;
+		sg->items[i].len = lens[i];
+		sg->items[i].dist = dists[i];
+		sg->items[i].df = dfs[i];
+		memcpy(str, terms[i], lens[i]);
+		str[lens[i]] = '\0';
+		str += lens[i] + 1;
+	}
+	return sg;
+}
+
+unsigned
+nxs_sugg_count(const nxs_sugg_t *sg)
+{
+	return sg->count;
+}
+
+uint64_t
+nxs_sugg_matches(const nxs_sugg_t *sg)
+{
+	return sg->matches;
+}
+
+bool
+nxs_sugg_dropped(const nxs_sugg_t *sg)
+{
+	return sg->dropped;
+}
+
+bool
+nxs_sugg_get(const nxs_sugg_t *sg, unsigned i, const char **term, size_t *len, unsigned *distance, uint64_t *df)
+{
+	if (i >= sg->count) {
+		return false;
+	}
+	if (term) *term = sg->items[i].term;
+	if (len) *len = sg->items[i].len;
+	if (distance) *distance = sg->items[i].dist;
+	if (df) *df = sg->items[i].df;
+	return true;
+}
+
+void
+nxs_sugg_release(nxs_sugg_t *sg)
+{
+	free(sg);
+}
+
+/* a JSON string: UTF-8 passes through; '"', '\\' and bytes < 0x20 (as \u00XX) are escaped */
+static size_t
+json_str(char *out, const char *s, size_t n)
+{
+	size_t o = 0;
+
+	out[o++] = '"';
+	for (size_t i = 0; i < n; i++) {
+		const unsigned char c = (unsigned char)s[i];
+		if (c == '"' || c == '\\') {
+			out[o++] = '\\';
+			out[o++] = (char)c;
+		} else if (c < 0x20) {
+			o += (size_t)sprintf(out + o, "\\u%04x", c);
+		} else {
+			out[o++] = (char)c;
+		}
+	}
+	out[o++] = '"';
+	return o;
+}
+
+/* {"token":"...","suggestions":[{"term":"...","distance":D,"df":N},...],"matches":M} */
+char *
+nxs_sugg_tojson(nxs_sugg_t *sg, size_t *len)
+{
+	size_t cap = 96 + 6 * sg->token_len, o = 0;
+	char *s;
+
+	for (unsigned i = 0; i < sg->count; i++) {
+		cap += 64 + 6 * sg->items[i].len;
+	}
+	if ((s = malloc(cap)) == NULL) {
+		return NULL;
+	}
+	o += (size_t)sprintf(s + o, "{\"token\":");
+	o += json_str(s + o, sg->token, sg->token_len);
+	o += (size_t)sprintf(s + o, ",\"suggestions\":[");
+	for (unsigned i = 0; i < sg->count; i++) {
+		o += (size_t)sprintf(s + o, "%s{\"term\":", i ? "," : "");
+		o += json_str(s + o, sg->items[i].term, sg->items[i].len);
+		o += (size_t)sprintf(s + o, ",\"distance\":%u,\"df\":%llu}", sg->items[i].dist,
+		    (unsigned long long)sg->items[i].df);
+	}
+	o += (size_t)sprintf(s + o, "],\"matches\":%llu}", (unsigned long long)sg->matches);
+	if (len) {
+		*len = o;
+	}
+	return s;
+}
+
+/* "suggest_limit" (1..NXS_SUGGEST_MAX, default 5), "suggest_maxdist" (1 or 2, default 2) */
+static int
+get_suggest_params(nxs_t *nxs, const nxs_params_t *params, unsigned *k, unsigned *maxdist)
+{
+	uint64_t v;
+
+	*k = 5;
+	*maxdist = LEVDIST_TOLERANCE;
+	if (!params) {
+		return 0;
+	}
+	if (nxs_params_get_uint(params, "suggest_limit", &v) == 0) {
+		if (v < 1 || v > NXS_SUGGEST_MAX) {
+			nxs_decl_err(nxs, NXS_ERR_INVALID, "invalid suggest_limit (1..%d)", NXS_SUGGEST_MAX);
+			return -1;
+		}
+		*k = (unsigned)v;
+	}
+	if (nxs_params_get_uint(params, "suggest_maxdist", &v) == 0) {
+		if (v < 1 || v > LEVDIST_TOLERANCE) {
+			nxs_decl_err(nxs, NXS_ERR_INVALID, "invalid suggest_maxdist (1 or 2)");
+			return -1;
+		}
+		*maxdist = (unsigned)v;
+	}
+	return 0;
+}
+
+/* lens: NULL = the strings are NUL-terminated */
+static int
+suggest_core(nxs_index_t *idx, nxs_params_t *params, const char *const *tokens, const size_t *lens, size_t n,
+    nxs_sugg_t **out, nxs_err_t *errs)
+{
+	nxs_t *nxs = idx->nxs;
+	unsigned k, maxdist;
+	char **val = NULL;
+	size_t *vlen = NULL, blen = 0, nd = 0;
+	int8_t *act = NULL;
+	uint8_t *bytes = NULL, *dist = NULL;
+	uint32_t *off = NULL, *ids = NULL, *df = NULL, *counts = NULL, *matches = NULL;
+	int ret = -1, failed = 0;
+
+	nxs_clear_error(nxs);
+	for (size_t i = 0; i < n; i++) {
+		out[i] = NULL;
+		if (errs) {
+			errs[i] = NXS_ERR_SUCCESS;
+		}
+	}
+	if (get_suggest_params(nxs, params, &k, &maxdist) == -1) {
+		return -1;
+	}
+	/* (a shard's dictionary and df are collection-wide, its postings are not: a follow-up, include/nxs.h) */
+	if (idx->n_shards) {
+		nxs_decl_err(nxs, NXS_ERR_INVALID, "suggest is not available on a doc shard");
+		return -1;
+	}
+	if (n > UINT32_MAX / 2) {
+		nxs_decl_err(nxs, NXS_ERR_LIMIT, "batch too large");
+		return -1;
+	}
+	/*
+	 * search.c:309-312, as every search does.  The call is local: with a communicator attached the
+	 * batches in flight can only be finished by all ranks together (resync_before_batch), so while
+	 * some are in flight this rank answers from the snapshot they run on.
+	 */
+	if (!(idx->comm && pend_oldest(idx)) && resync_before_batch(idx) == -1) {
+		return -1;
+	}
+	/* new terms reach the BK image first.  (A batch whose fuzzy pass is still on the device reads the
+	 * image: it was synced for that pass, and nothing can have moved since without finishing the batch --
+	 * should the image be stale all the same, the pass is waited for before it is replaced.) */
+	if (idx->bk_upto != idx->last_id || idx->bk_flags_stale) {
+		(void)late_finish(idx);
+		if (nxs_index_bk_sync(idx) == -1) {
+			return -1;
+		}
+	}
+	val = calloc(n ? n : 1, sizeof(*val));
+	vlen = calloc(n ? n : 1, sizeof(*vlen));
+	act = calloc(n ? n : 1, sizeof(*act));
+	off = malloc((n + 1) * sizeof(*off));
+	if (!val || !vlen || !act || !off) {
+		nxs_decl_err(nxs, NXS_ERR_SYSTEM, "out of memory");
+		goto out;
+	}
+	/* the filters a query token goes through (tokenizer.c:205-227): normalizer, stop words, stemmer */
+	for (size_t i = 0; i < n; i++) {
+		size_t len = lens ? lens[i] : strlen(tokens[i]);
+
+		if ((val[i] = malloc(len + 1)) == NULL) {
+			nxs_decl_err(nxs, NXS_ERR_SYSTEM, "out of memory");
+			goto out;
+		}
+		memcpy(val[i], tokens[i], len);
+		val[i][len] = '\0';
+		act[i] = 1;
+		if (idx->filters) {
+			act[i] = (int8_t)nxs_filters_run(idx->filters, &val[i], &len);
+		} else if (idx->lowercase) {
+			for (size_t c = 0; c < len; c++) {
+				if (val[i][c] >= 'A' && val[i][c] <= 'Z') {
+					val[i][c] += 32;
+				}
+			}
+		}
+		vlen[i] = len;
+		if (act[i] == 1) {
+			blen += len;
+			nd++;
+		}
+	}
+	if (blen > UINT32_MAX / 2) {
+		nxs_decl_err(nxs, NXS_ERR_LIMIT, "batch too large");
+		goto out;
+	}
+	bytes = malloc(blen + 16);
+	ids = malloc((nd * k + 1) * sizeof(*ids));
+	df = malloc((nd * k + 1) * sizeof(*df));
+	dist = malloc(nd * k + 1);
+	counts = malloc((nd + 1) * sizeof(*counts));
+	matches = malloc((nd + 1) * sizeof(*matches));
+	if (!bytes || !ids || !df || !dist || !counts || !matches) {
+		nxs_decl_err(nxs, NXS_ERR_SYSTEM, "out of memory");
+		goto out;
+	}
+	blen = 0;
+	nd = 0;
+	for (size_t i = 0; i < n; i++) {
+		if (act[i] == 1) {
+			off[nd++] = (uint32_t)blen;
+			memcpy(bytes + blen, val[i], vlen[i]);
+			blen += vlen[i];
+		}
+	}
+	off[nd] = (uint32_t)blen;
+	if (nd && nxsgpu_suggest(idx->dev, bytes, off, (uint32_t)nd, maxdist, k, ids, dist, df, counts, matches) != 0) {
+		nxs_decl_err(nxs, NXS_ERR_FATAL, "device suggest pass failed: %s", nxsgpu_last_error());
+		goto out;
+	}
+	nd = 0;
+	for (size_t i = 0; i < n; i++) {
+		const uint8_t *terms[NXS_SUGGEST_MAX];
+		size_t tlens[NXS_SUGGEST_MAX];
+		unsigned dists[NXS_SUGGEST_MAX];
+		uint64_t dfs[NXS_SUGGEST_MAX];
+
+		if (act[i] < 0) {
+			/* FILT_ERROR: what fails a query (search.c:199-203) fails this token */
+			if (errs) {
+				errs[i] = NXS_ERR_FATAL;
+			}
+			nxs_decl_err(nxs, NXS_ERR_FATAL, "the filters failed on token %zu", i);
+			failed++;
+			continue;
+		}
+		if (act[i] == 0) {
+			out[i] = sugg_build("", 0, true, 0, 0, NULL, NULL, NULL, NULL);
+		} else {
+			const unsigned c = counts[nd];
+			bool bad = false;
+
+			for (unsigned j = 0; j < c; j++) {
+				const uint32_t id = ids[nd * k + j];
+				if (id < 1 || id > idx->last_id) {
+					bad = true;
+					break;
+				}
+				terms[j] = idx->terms[id].val;
+				tlens[j] = idx->terms[id].len;
+				dists[j] = dist[nd * k + j];
+				dfs[j] = df[nd * k + j];
+			}
+			if (bad) {
+				if (errs) {
+					errs[i] = NXS_ERR_FATAL;
+				}
+				nxs_decl_err(nxs, NXS_ERR_FATAL, "the device named an unknown term for token %zu", i);
+				failed++;
+				nd++;
+				continue;
+			}
+			out[i] = sugg_build(val[i], vlen[i], false, matches[nd], c, terms, tlens, dists, dfs);
+			nd++;
+		}
+		if (!out[i]) {
+			if (errs) {
+				errs[i] = NXS_ERR_SYSTEM;
+			}
+			nxs_decl_err(nxs, NXS_ERR_SYSTEM, "out of memory");
+			failed++;
+		}
+	}
+	ret = failed;
+out:
+	for (size_t i = 0; val && i < n; i++) {
+		free(val[i]);
+	}
+	free(val);
+	free(vlen);
+	free(act);
+	free(off);
+	free(bytes);
+	free(ids);
+	free(df);
+	free(dist);
+	free(counts);
+	free(matches);
+	return ret;
+}
+
+int
+nxs_index_suggest_batch(nxs_index_t *idx, nxs_params_t *params, const char *const *tokens, size_t n,
+    nxs_sugg_t **out, nxs_err_t *errs)
+{
+	return suggest_core(idx, params, tokens, NULL, n, out, errs);
+}
+
+nxs_sugg_t *
+nxs_index_suggest(nxs_index_t *idx, nxs_params_t *params, const char *token, size_t len)
+{
+	nxs_sugg_t *sg = NULL;
+	const char *tv[1] = { token };
+
+	if (suggest_core(idx, params, tv, &len, 1, &sg, NULL) != 0) {
+		if (sg) {
+			nxs_sugg_release(sg);
+		}
+		return NULL;
+	}
+	return sg;
+}
+
+#ifdef NXS_TEST_HOOKS
+/* the host ranker (nxs_suggest.h) over a dictionary handed in: term i has id i + 1 */
+void
+nxs_test_suggest_host(const uint8_t *const *terms, const uint32_t *lens, const uint32_t *dfs, uint32_t n_terms,
+    const uint8_t *token, size_t len, uint32_t maxdist, uint32_t k, uint32_t *out_ids, uint8_t *out_dist,
+    uint32_t *out_df, uint32_t *count, uint32_t *matches)
+{
+	nxs_suggest_rank(terms, lens, dfs, NULL, n_terms, token, len, maxdist, k, out_ids, out_dist, out_df, count, matches);
+}
+
+/* the parameters as nxs_index_suggest reads them: 0, or -1 with the error declared */
+int
+nxs_test_suggest_params(nxs_t *nxs, nxs_params_t *params, unsigned *k, unsigned *maxdist)
+{
+	nxs_clear_error(nxs);
+	return get_suggest_params(nxs, params, k, maxdist);
+}
+
+/* an nxs_sugg_t built by hand (the accessors and the JSON writer without an index) */
+nxs_sugg_t *
+nxs_test_sugg_build(const char *token, size_t token_len, bool dropped, uint64_t matches, unsigned count,
+    const uint8_t *const *terms, const size_t *lens, const unsigned *dists, const uint64_t *dfs)
+{
+	return sugg_build(token, token_len, dropped, matches, count, terms, lens, dists, dfs);
+}
+#endif
 
 /* ---- N4: doc-sharded collections --------------------------------------------------- */
 

@@ -1204,3 +1204,635 @@ fuzzy_search(nxsgpu_index_t *ix, const uint8_t *tok_bytes, const uint32_t *tok_o
 	}
 	return 0;
 }
+
+/* ---- spelling suggestions -------------------------------------------- */
+/*
+ * nxsgpu_suggest: for every token the dictionary terms within maxdist (1 or 2) that have a posting in a
+ * live doc, best k by (distance ascending, df descending, term id ascending), and how many there are.
+ *
+ * The match-first search above already screens every (token, term) pair and takes the exact distance of
+ * every survivor; it keeps the one term bktree_search would pick.  This pass keeps them all:
+ *
+ *   candidates   a permutation of its own beside d_fz_node: every node whose term has df > 0 (the CSR's
+ *                live posting count) and at most FZ_MAXLEN bytes -- whether or not the BK walk reaches it
+ *                (slot-63 subtrees) and whatever the on-disk total says -- sorted by length; built on the
+ *                first call and again when nxsgpu_index::sg_gen has moved
+ *   k_fz_filter  unchanged, on those arrays: survivors into the FZ_NQ sub-queues
+ *   k_sg_dist    exact distance; d <= maxdist bumps the token's counter and appends (token, d, node) to
+ *                the match queue (one returning atomic per workgroup and round)
+ *   k_sg_scan    exclusive scan of the counters: a segment per token
+ *   k_sg_scatter the queue into the segments, as sort keys: d << 32 | ~df, term id
+ *   k_sg_select  one wavefront per token, k rounds of a wave-wide minimum over the segment (the keys are
+ *                distinct: a total order, so the result does not depend on queue order)
+ *
+ * A queue that overflows is never a wrong answer: the pass is repeated with a quarter of the tokens, and
+ * a single token that still overflows gets queues sized to what the screen can emit at most (8 bytes x
+ * candidates).  Tokens beyond the bit-vector distance and everything under NXS_GPU_SUGGEST=host take the
+ * host ranker (nxs_suggest.h) over a host copy of the BK image.
+ */
+#include "nxs_suggest.h"
+
+struct sg_key_t { uint64_t hi, lo; };		/* d << 32 | ~df, term id */
+
+struct sg_state_t {
+	bool		built;
+	uint64_t	built_gen;
+	uint32_t *	d_node;		/* [n_c] candidates, sorted by term length */
+	uint32_t *	d_sig;
+	uint8_t *	d_len;
+	uint32_t	n_c;
+	/* the host ranker's dictionary: every node with df > 0, any length */
+	std::vector<nxsgpu_bknode_t> h_nodes;
+	std::vector<uint8_t> h_bytes;
+	std::vector<const uint8_t *> h_terms;
+	std::vector<uint32_t> h_lens, h_dfs, h_ids;
+	hipStream_t	st;
+	void *		ws;
+	size_t		ws_len;
+	uint8_t *	pin;
+	size_t		pin_len;
+	hipEvent_t	ev[5];
+	bool		ev_ok;
+	double		prof[NXSGPU_SUGGEST_PROF];
+};
+
+#define	SG_TOK_BITS	30
+#define	SG_TOK_MASK	((1u << SG_TOK_BITS) - 1)
+
+__global__ void __launch_bounds__(1024)
+k_sg_dist(const fz_args_t A, const fz_item_t *cand, const uint32_t *cand_count, uint32_t qcap, uint32_t maxdist,
+    uint32_t *tok_matches, uint2 *match, uint32_t *match_count, uint32_t mcap)
+{
+	__shared__ uint32_t s_wtot[16], s_base;
+	const unsigned wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
+	const uint32_t count = min(cand_count[blockIdx.y * FZ_CSTRIDE], qcap);
+	const uint32_t nthreads = gridDim.x * blockDim.x;
+	const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
+	const uint32_t rounds = (count + nthreads - 1) / nthreads;
+
+	cand += (uint64_t)blockIdx.y * qcap;
+	for (uint32_t r = 0; r < rounds; r++) {
+		const uint32_t i = r * nthreads + tid;
+		uint2 mi = make_uint2(0, 0);
+		bool hit = false;
+
+		if (i < count) {
+			const fz_item_t it = cand[i];
+			const nxsgpu_bknode_t nd = A.bk[it.node];
+			const int d = fz_distance(A, it.tok, nd, 0);
+			if ((uint32_t)d <= maxdist) {
+				hit = true;
+				mi = make_uint2(it.tok | ((uint32_t)d << SG_TOK_BITS), it.node);
+				atomicAdd(&tok_matches[it.tok], 1u);
+			}
+		}
+		const uint64_t m = ballot64(hit);
+		s_wtot[wid] = __popcll(m);
+		__syncthreads();
+		if (threadIdx.x == 0) {
+			uint32_t sum = 0;
+			for (unsigned w = 0; w < nw; w++) {
+				const uint32_t tw = s_wtot[w];
+				s_wtot[w] = sum;
+				sum += tw;
+			}
+			s_base = sum ? atomicAdd(match_count, sum) : 0;
+		}
+		__syncthreads();
+		const uint32_t o = s_base + s_wtot[wid] + lanes_below(m);
+		__syncthreads();
+		if (hit) {
+			if (o < mcap) {
+				match[o] = mi;
+			} else {
+				*A.overflow = 1;
+			}
+		}
+	}
+}
+
+/* seg_off[i] = sum of cnt[0 .. i), seg_off[n] = the total; fill[] = 0 (one workgroup) */
+__global__ void __launch_bounds__(1024)
+k_sg_scan(const uint32_t *cnt, uint32_t n, uint32_t *seg_off, uint32_t *fill)
+{
+	__shared__ uint32_t s_w[16], s_carry;
+	const unsigned lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+
+	if (threadIdx.x == 0) {
+		s_carry = 0;
+	}
+	__syncthreads();
+	for (uint32_t base = 0; base < n; base += 1024) {
+		const uint32_t i = base + threadIdx.x;
+		const uint32_t v = i < n ? cnt[i] : 0;
+		uint32_t incl = v, woff = 0;
+		for (int o = 1; o < WAVE; o <<= 1) {
+			const uint32_t u = (uint32_t)__shfl_up((int)incl, o);
+			if (lane >= (unsigned)o) incl += u;
+		}
+		if (lane == WAVE - 1) {
+			s_w[wid] = incl;
+		}
+		__syncthreads();
+		for (unsigned w = 0; w < wid; w++) {
+			woff += s_w[w];
+		}
+		const uint32_t carry = s_carry;
+		if (i < n) {
+			seg_off[i] = carry + woff + incl - v;
+			fill[i] = 0;
+		}
+		__syncthreads();
+		if (threadIdx.x == 1023) {
+			s_carry = carry + woff + incl;
+		}
+		__syncthreads();
+	}
+	if (threadIdx.x == 0) {
+		seg_off[n] = s_carry;
+	}
+}
+
+/* the match queue into the tokens' segments, as sort keys; df = the CSR's live posting count */
+__global__ void __launch_bounds__(256)
+k_sg_scatter(const nxsgpu_bknode_t *__restrict__ bk, const uint64_t *__restrict__ post_off, uint32_t n_terms,
+    const uint2 *__restrict__ match, const uint32_t *__restrict__ match_count, uint32_t mcap,
+    const uint32_t *__restrict__ seg_off, uint32_t *fill, sg_key_t *keys)
+{
+	const uint32_t count = min(*match_count, mcap);
+	const uint32_t nthreads = gridDim.x * blockDim.x;
+
+	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += nthreads) {
+		const uint2 m = match[i];
+		const uint32_t tok = m.x & SG_TOK_MASK, d = m.x >> SG_TOK_BITS;
+		const uint32_t term = bk[m.y].term_id;
+		const uint32_t df = (term >= 1 && term <= n_terms) ? (uint32_t)(post_off[term + 1] - post_off[term]) : 0;
+		const uint32_t pos = seg_off[tok] + atomicAdd(&fill[tok], 1u);
+		sg_key_t key;
+
+		key.hi = ((uint64_t)d << 32) | (uint32_t)~df;
+		key.lo = term;
+		/* (inside the segment always; inside the array unless the match queue overflowed: that pass's
+		 * counters say more than the queue holds, and its rows are discarded) */
+		if (pos < seg_off[tok + 1] && pos < mcap) {
+			keys[pos] = key;
+		}
+	}
+}
+
+static __device__ __forceinline__ bool
+sg_less(const sg_key_t &a, const sg_key_t &b)
+{
+	return a.hi < b.hi || (a.hi == b.hi && a.lo < b.lo);
+}
+
+/*
+ * One wavefront per token: round r delivers the r-th smallest key of the segment -- the smallest one
+ * above the previous round's (the keys are distinct: a term appears once).  Every lane looks at its
+ * stride of the segment (its first item stays in registers: segments of up to 64 matches, nearly all of
+ * them, are read once), the 64 candidates meet in a butterfly.  Exact for segments of any length.
+ */
+__global__ void __launch_bounds__(64)
+k_sg_select(const sg_key_t *__restrict__ keys, const uint32_t *__restrict__ seg_off, uint32_t mcap, uint32_t k,
+    uint32_t *term_ids, uint8_t *dist, uint32_t *df, uint32_t *counts)
+{
+	const uint32_t tok = blockIdx.x;
+	const unsigned lane = threadIdx.x;
+	/* (a segment that ends beyond the array belongs to an overflowed pass: nothing to select) */
+	const uint32_t s = seg_off[tok], e = seg_off[tok + 1], n = e <= mcap ? e - s : 0;
+	const uint32_t nout = min(k, n);
+	const sg_key_t none = { ~0ull, ~0ull };
+	sg_key_t mine = none, prev = none;
+
+	if (lane < n) {
+		mine = keys[s + lane];
+	}
+	for (uint32_t r = 0; r < nout; r++) {
+		sg_key_t best = none;
+
+		if (lane < n && (r == 0 || sg_less(prev, mine))) {
+			best = mine;
+		}
+		for (uint32_t i = lane + WAVE; i < n; i += WAVE) {
+			const sg_key_t c = keys[s + i];
+			if ((r == 0 || sg_less(prev, c)) && sg_less(c, best)) {
+				best = c;
+			}
+		}
+		for (int o = 32; o; o >>= 1) {
+			sg_key_t c;
+			c.hi = (uint64_t)__shfl_xor((long long)best.hi, o);
+			c.lo = (uint64_t)__shfl_xor((long long)best.lo, o);
+			if (sg_less(c, best)) {
+				best = c;
+			}
+		}
+		if (lane == 0) {
+			const uint64_t at = (uint64_t)tok * k + r;
+			term_ids[at] = (uint32_t)best.lo;
+			dist[at] = (uint8_t)(best.hi >> 32);
+			df[at] = ~(uint32_t)best.hi;
+		}
+		prev = best;
+	}
+	if (lane == 0) {
+		counts[tok] = nout;
+	}
+}
+
+void
+sg_free(nxsgpu_index_t *ix)
+{
+	sg_state_t *sg = ix->sg;
+
+	if (!sg) {
+		return;
+	}
+	if (sg->st) {
+		(void)hipStreamSynchronize(sg->st);
+		(void)hipStreamDestroy(sg->st);
+	}
+	for (int i = 0; sg->ev_ok && i < 5; i++) {
+		(void)hipEventDestroy(sg->ev[i]);
+	}
+	(void)hipFree(sg->d_node);
+	(void)hipFree(sg->d_sig);
+	(void)hipFree(sg->d_len);
+	(void)hipFree(sg->ws);
+	if (sg->pin) {
+		(void)hipHostFree(sg->pin);
+	}
+	delete sg;
+	ix->sg = NULL;
+}
+
+/* the state, and the candidates of the index's current generation */
+static int
+sg_prepare(nxsgpu_index_t *ix)
+{
+	sg_state_t *sg = ix->sg;
+
+	if (!sg) {
+		sg = new sg_state_t();
+		if (hipStreamCreateWithFlags(&sg->st, hipStreamNonBlocking) != hipSuccess) {
+			delete sg;
+			set_error("suggest: no stream");
+			return -1;
+		}
+		ix->sg = sg;
+	}
+	if (ix->profiling && !sg->ev_ok) {
+		bool ok = true;
+		for (int i = 0; i < 5 && ok; i++) {
+			ok = hipEventCreate(&sg->ev[i]) == hipSuccess;
+		}
+		if (!ok) {
+			set_error("suggest: no events");
+			return -1;
+		}
+		sg->ev_ok = true;
+	}
+	if (sg->built && sg->built_gen == ix->sg_gen) {
+		return 0;
+	}
+	sg->built = false;
+	(void)hipFree(sg->d_node);
+	(void)hipFree(sg->d_sig);
+	(void)hipFree(sg->d_len);
+	sg->d_node = sg->d_sig = NULL;
+	sg->d_len = NULL;
+	sg->n_c = 0;
+	sg->h_terms.clear();
+	sg->h_lens.clear();
+	sg->h_dfs.clear();
+	sg->h_ids.clear();
+
+	const uint32_t n = ix->n_bk;
+	sg->h_nodes.resize(n);
+	uint64_t blen = 0;
+	if (n && hipMemcpy(sg->h_nodes.data(), ix->d_bk, (size_t)n * sizeof(nxsgpu_bknode_t), hipMemcpyDeviceToHost) != hipSuccess) {
+		set_error("suggest: reading the BK image back failed");
+		return -1;
+	}
+	for (uint32_t i = 0; i < n; i++) {
+		blen = std::max<uint64_t>(blen, (uint64_t)sg->h_nodes[i].str_off + sg->h_nodes[i].str_len);
+	}
+	sg->h_bytes.resize(blen + 16);
+	if (blen && hipMemcpy(sg->h_bytes.data(), ix->d_bk_bytes, blen, hipMemcpyDeviceToHost) != hipSuccess) {
+		set_error("suggest: reading the BK image back failed");
+		return -1;
+	}
+	/* df > 0: the live posting count of the CSR (what nxsgpu_index_df reports) */
+	auto df_of = [&](uint32_t i) -> uint32_t {
+		const uint32_t t = sg->h_nodes[i].term_id;
+		return (t >= 1 && t <= ix->n_terms) ? (uint32_t)(ix->h_post_off[(size_t)t + 1] - ix->h_post_off[t]) : 0;
+	};
+	std::vector<uint32_t> start(FZ_MAXLEN + 2, 0), perm;
+	uint32_t n_c = 0;
+	for (uint32_t i = 0; i < n; i++) {
+		const uint32_t df = df_of(i);
+		if (!df) {
+			continue;
+		}
+		sg->h_terms.push_back(sg->h_bytes.data() + sg->h_nodes[i].str_off);
+		sg->h_lens.push_back(sg->h_nodes[i].str_len);
+		sg->h_dfs.push_back(df);
+		sg->h_ids.push_back(sg->h_nodes[i].term_id);
+		if (sg->h_nodes[i].str_len <= FZ_MAXLEN) {
+			start[sg->h_nodes[i].str_len + 1]++;
+			n_c++;
+		}
+	}
+	for (uint32_t l = 0; l <= FZ_MAXLEN; l++) {
+		start[l + 1] += start[l];
+	}
+	perm.resize(std::max<uint32_t>(n_c, 1));
+	for (uint32_t i = 0; i < n; i++) {
+		if (df_of(i) && sg->h_nodes[i].str_len <= FZ_MAXLEN) {
+			perm[start[sg->h_nodes[i].str_len]++] = i;
+		}
+	}
+	if (n_c) {
+		if (hipMalloc(&sg->d_node, (size_t)n_c * 4) != hipSuccess ||
+		    hipMalloc(&sg->d_sig, (size_t)n_c * 4) != hipSuccess ||
+		    hipMalloc(&sg->d_len, (size_t)n_c + 16) != hipSuccess ||
+		    hipMemcpyAsync(sg->d_node, perm.data(), (size_t)n_c * 4, hipMemcpyHostToDevice, sg->st) != hipSuccess) {
+			set_error("suggest candidates: out of device memory");
+			return -1;
+		}
+		hipLaunchKernelGGL(k_fz_sigs, dim3((n_c + 255) / 256), dim3(256), 0, sg->st,
+		    ix->d_bk, ix->d_bk_bytes, sg->d_node, n_c, sg->d_sig, sg->d_len);
+		if (hipGetLastError() != hipSuccess || hipStreamSynchronize(sg->st) != hipSuccess) {
+			set_error("suggest candidates: k_fz_sigs failed");
+			return -1;
+		}
+	}
+	sg->n_c = n_c;
+	sg->built = true;
+	sg->built_gen = ix->sg_gen;
+	return 0;
+}
+
+/*
+ * One device pass over tokens [0, n_tok) (every one <= NXS_MYERS_MAXPAT bytes; tok_off[0] need not be 0):
+ * one upload from pinned memory, the kernels, one copy back; blocking.  `full`: queues sized to what the
+ * screen can emit at most.  0 = rows written, 1 = a queue overflowed (nothing written), -1 = error.
+ */
+static int
+sg_pass(nxsgpu_index_t *ix, const uint8_t *tok_bytes, const uint32_t *tok_off, uint32_t n_tok, bool full,
+    uint32_t maxdist, uint32_t k, const uint32_t *dest, uint32_t *o_ids, uint8_t *o_dist, uint32_t *o_df,
+    uint32_t *o_counts, uint32_t *o_matches)
+{
+	sg_state_t *sg = ix->sg;
+	const uint32_t n_c = sg->n_c;
+	const uint32_t blen = tok_off[n_tok] - tok_off[0];
+	const uint32_t gy = std::max<uint32_t>(1, std::min<uint32_t>(8, n_tok / 128));
+	/* (what a sub-queue can receive at most: mf_launch) */
+	const uint64_t q_most = (uint64_t)gy * (((n_c + 255) / 256 + FZ_NQ - 1) / FZ_NQ) * 256 * ((n_tok + gy - 1) / gy);
+	const uint64_t qcap = std::min<uint64_t>(0xffffffffu / FZ_NQ, std::max<uint64_t>(16,
+	    full ? q_most : std::min<uint64_t>(ix->cfg.fuzzy_cand / FZ_NQ, q_most)));
+	const uint64_t ccap = qcap * FZ_NQ;
+	/* (matches are survivors: a single token's match queue cannot overflow before its survivor queues do) */
+	const uint64_t mcap = n_tok == 1 ? ccap : std::max<uint64_t>(1024, ccap / 4);
+	const size_t rows = (size_t)n_tok * k;
+	/* up: offsets | rank in the length-sorted order | first rank of every length | bytes (mf_launch) */
+	const size_t up_words = (size_t)n_tok + 1 + n_tok + NXS_MYERS_MAXPAT + 2;
+	const size_t up_bytes = (up_words * 4 + 15) & ~(size_t)15;
+	/* down: term ids | df | counts | matches | counters (-, matches queued, overflow, -) | survivors per
+	 * sub-queue | distances */
+	const size_t dn_words = rows * 2 + (size_t)n_tok * 2 + 4 + FZ_NQ * FZ_CSTRIDE;
+	const size_t dn_bytes = (dn_words * 4 + rows + 15) & ~(size_t)15;
+	const size_t pin_need = up_bytes + ((blen + 16 + 15) & ~(size_t)15) + dn_bytes + 64;
+	const size_t need = ccap * sizeof(fz_item_t) + mcap * (sizeof(uint2) + sizeof(sg_key_t)) + dn_bytes +
+	    (size_t)n_tok * (256 * 8 + 8 + 4 + 4) + 64 + up_bytes + blen + 16 + 16 * 256;
+	hipStream_t st = sg->st;
+	const bool prof = ix->profiling && sg->ev_ok;
+
+	if (sg->pin_len < pin_need) {
+		if (sg->pin) {
+			(void)hipHostFree(sg->pin);
+			sg->pin = NULL;
+			sg->pin_len = 0;
+		}
+		if (hipHostMalloc((void **)&sg->pin, pin_need + pin_need / 2, hipHostMallocDefault) != hipSuccess) {
+			set_error("hipHostMalloc(%zu) for the suggest staging failed", pin_need);
+			return -1;
+		}
+		sg->pin_len = pin_need + pin_need / 2;
+	}
+	if (sg->ws_len < need) {
+		if (sg->ws) {
+			(void)hipFree(sg->ws);
+			sg->ws = NULL;
+			sg->ws_len = 0;
+		}
+		if (hipMalloc(&sg->ws, need) != hipSuccess) {
+			set_error("hipMalloc(%zu) for the suggest workspace failed", need);
+			return -1;
+		}
+		sg->ws_len = need;
+	}
+	uint32_t *const up = (uint32_t *)sg->pin;
+	uint8_t *const h_dn = sg->pin + up_bytes + ((blen + 16 + 15) & ~(size_t)15);
+	uint32_t *roff = up, *rank = roff + n_tok + 1, *len_off = rank + n_tok;
+
+	uint8_t *p = (uint8_t *)sg->ws;
+	fz_item_t *d_cand = carve<fz_item_t>(p, ccap);
+	uint2 *d_match = carve<uint2>(p, mcap);
+	sg_key_t *d_keys = carve<sg_key_t>(p, mcap);
+	uint8_t *d_dn = carve<uint8_t>(p, dn_bytes);
+	uint32_t *d_ids = (uint32_t *)d_dn, *d_df = d_ids + rows, *d_counts = d_df + rows, *d_matches = d_counts + n_tok;
+	uint32_t *d_cnt = d_matches + n_tok, *d_qcnt = d_cnt + 4;
+	uint8_t *d_dist = (uint8_t *)(d_qcnt + FZ_NQ * FZ_CSTRIDE);
+	uint64_t *d_peq = carve<uint64_t>(p, (size_t)n_tok * 256);
+	uint2 *d_tokf = carve<uint2>(p, (size_t)n_tok + 4);
+	uint32_t *d_segoff = carve<uint32_t>(p, (size_t)n_tok + 1);
+	uint32_t *d_fill = carve<uint32_t>(p, n_tok);
+	uint8_t *d_upb = carve<uint8_t>(p, up_bytes + blen + 16);
+	uint32_t *d_up = (uint32_t *)d_upb;
+	uint8_t *d_bytes = d_upb + up_bytes;
+	uint32_t *d_off = d_up, *d_rank = d_up + n_tok + 1, *d_len_off = d_rank + n_tok;
+	fz_args_t fa;
+
+	for (uint32_t i = 0; i <= n_tok; i++) {
+		roff[i] = tok_off[i] - tok_off[0];
+	}
+	for (uint32_t l = 0; l <= NXS_MYERS_MAXPAT + 1; l++) {
+		len_off[l] = 0;
+	}
+	for (uint32_t i = 0; i < n_tok; i++) {
+		len_off[roff[i + 1] - roff[i] + 1]++;		/* (every token is <= 64 bytes here) */
+	}
+	for (uint32_t l = 0; l <= NXS_MYERS_MAXPAT; l++) {
+		len_off[l + 1] += len_off[l];
+	}
+	{
+		uint32_t next[NXS_MYERS_MAXPAT + 2];
+		memcpy(next, len_off, sizeof(next));
+		for (uint32_t i = 0; i < n_tok; i++) {
+			rank[i] = next[roff[i + 1] - roff[i]]++;
+		}
+	}
+	memcpy(sg->pin + up_bytes, tok_bytes + tok_off[0], blen);
+	if (hipMemcpyAsync(d_upb, sg->pin, up_bytes + blen, hipMemcpyHostToDevice, st) != hipSuccess ||
+	    hipMemsetAsync(d_dn, 0, dn_bytes, st) != hipSuccess ||
+	    hipMemsetAsync(d_tokf + n_tok, 0xff, 4 * sizeof(uint2), st) != hipSuccess) {
+		set_error("suggest upload failed");
+		return -1;
+	}
+	if (prof) (void)hipEventRecord(sg->ev[0], st);
+	hipLaunchKernelGGL(k_bk_peq, dim3(n_tok), dim3(256), 0, st, d_bytes, d_off, n_tok, d_peq, d_tokf, d_rank);
+	hipLaunchKernelGGL(k_fz_filter, dim3((n_c + 255) / 256, gy), dim3(256), 0, st,
+	    sg->d_sig, sg->d_node, sg->d_len, n_c, d_tokf, d_len_off, d_cand, d_qcnt, (uint32_t)qcap, d_cnt + 2);
+	if (prof) (void)hipEventRecord(sg->ev[1], st);
+	memset(&fa, 0, sizeof(fa));
+	fa.bk = ix->d_bk;
+	fa.bk_bytes = ix->d_bk_bytes;
+	fa.tok_bytes = d_bytes;
+	fa.tok_off = d_off;
+	fa.peq = d_peq;
+	fa.cap = (uint32_t)ccap;
+	fa.overflow = d_cnt + 2;
+	hipLaunchKernelGGL(k_sg_dist, dim3(8, FZ_NQ), dim3(1024), 0, st, fa, d_cand, d_qcnt, (uint32_t)qcap, maxdist,
+	    d_matches, d_match, d_cnt + 1, (uint32_t)mcap);
+	if (prof) (void)hipEventRecord(sg->ev[2], st);
+	hipLaunchKernelGGL(k_sg_scan, dim3(1), dim3(1024), 0, st, d_matches, n_tok, d_segoff, d_fill);
+	hipLaunchKernelGGL(k_sg_scatter, dim3(512), dim3(256), 0, st, ix->d_bk, ix->d_post_off, ix->n_terms,
+	    d_match, d_cnt + 1, (uint32_t)mcap, d_segoff, d_fill, d_keys);
+	if (prof) (void)hipEventRecord(sg->ev[3], st);
+	hipLaunchKernelGGL(k_sg_select, dim3(n_tok), dim3(64), 0, st, d_keys, d_segoff, (uint32_t)mcap, k, d_ids, d_dist, d_df, d_counts);
+	if (prof) (void)hipEventRecord(sg->ev[4], st);
+	if (hipGetLastError() != hipSuccess) {
+		set_error("suggest kernel launch failed");
+		(void)hipStreamSynchronize(st);
+		return -1;
+	}
+	/* (an overflowed pass: k_sg_scatter and k_sg_select stay inside the arrays -- they check against mcap --
+	 * and the rows are thrown away below) */
+	if (hipMemcpyAsync(h_dn, d_dn, dn_bytes, hipMemcpyDeviceToHost, st) != hipSuccess ||
+	    hipStreamSynchronize(st) != hipSuccess) {
+		set_error("suggest pass failed: %s", hipGetErrorString(hipGetLastError()));
+		return -1;
+	}
+	const uint32_t *h_ids = (const uint32_t *)h_dn, *h_df = h_ids + rows, *h_counts = h_df + rows, *h_matches = h_counts + n_tok;
+	const uint32_t *h_cnt = h_matches + n_tok, *h_qcnt = h_cnt + 4;
+	const uint8_t *h_dist = (const uint8_t *)(h_qcnt + FZ_NQ * FZ_CSTRIDE);
+	if (prof) {
+		float ms = 0;
+		sg->prof[0] += 1;
+		(void)hipEventElapsedTime(&ms, sg->ev[0], sg->ev[4]);
+		sg->prof[1] += ms;
+		for (int i = 0; i < 4; i++) {
+			(void)hipEventElapsedTime(&ms, sg->ev[i], sg->ev[i + 1]);
+			sg->prof[2 + i] += ms;
+		}
+	}
+	if (h_cnt[2]) {
+		sg->prof[9] += 1;
+		return 1;
+	}
+	if (prof) {
+		for (uint32_t q = 0; q < FZ_NQ; q++) {
+			sg->prof[6] += h_qcnt[q * FZ_CSTRIDE];
+		}
+		sg->prof[7] += h_cnt[1];
+	}
+	for (uint32_t i = 0; i < n_tok; i++) {
+		const size_t to = (size_t)dest[i] * k, from = (size_t)i * k;
+		memcpy(o_ids + to, h_ids + from, (size_t)k * 4);
+		memcpy(o_df + to, h_df + from, (size_t)k * 4);
+		memcpy(o_dist + to, h_dist + from, k);
+		o_counts[dest[i]] = h_counts[i];
+		o_matches[dest[i]] = h_matches[i];
+	}
+	return 0;
+}
+
+extern "C" int
+nxsgpu_suggest(nxsgpu_index_t *ix, const uint8_t *tok_bytes, const uint32_t *tok_off, uint32_t n_tok,
+    uint32_t maxdist, uint32_t k, uint32_t *term_ids, uint8_t *dist, uint32_t *df, uint32_t *counts,
+    uint32_t *matches)
+{
+	if (k < 1 || k > NXS_SUGGEST_MAX || maxdist < 1 || maxdist > 2) {
+		set_error("nxsgpu_suggest: k is 1..%d, maxdist 1 or 2", NXS_SUGGEST_MAX);
+		return -1;
+	}
+	if (n_tok == 0) {
+		return 0;
+	}
+	if (hipSetDevice(ix->device) != hipSuccess) {
+		set_error("hipSetDevice failed");
+		return -1;
+	}
+	if (sg_prepare(ix) != 0) {
+		return -1;
+	}
+	sg_state_t *sg = ix->sg;
+	std::vector<uint32_t> dest, off;
+	std::vector<uint8_t> bytes;
+
+	memset(term_ids, 0, (size_t)n_tok * k * 4);
+	memset(df, 0, (size_t)n_tok * k * 4);
+	memset(dist, 0, (size_t)n_tok * k);
+	memset(counts, 0, (size_t)n_tok * 4);
+	memset(matches, 0, (size_t)n_tok * 4);
+	off.push_back(0);
+	for (uint32_t i = 0; i < n_tok; i++) {
+		const uint32_t m = tok_off[i + 1] - tok_off[i];
+		if (ix->cfg.suggest_host || m > NXS_MYERS_MAXPAT) {
+#if !defined(__HIP_DEVICE_COMPILE__)	/* (nxs_lev.h keeps its host functions out of the device pass) */
+			nxs_suggest_rank(sg->h_terms.data(), sg->h_lens.data(), sg->h_dfs.data(), sg->h_ids.data(),
+			    sg->h_terms.size(), tok_bytes + tok_off[i], m, maxdist, k, term_ids + (size_t)i * k,
+			    dist + (size_t)i * k, df + (size_t)i * k, &counts[i], &matches[i]);
+#endif
+			sg->prof[8] += 1;
+			continue;
+		}
+		dest.push_back(i);
+		bytes.insert(bytes.end(), tok_bytes + tok_off[i], tok_bytes + tok_off[i + 1]);
+		off.push_back((uint32_t)bytes.size());
+	}
+	const uint32_t nd = (uint32_t)dest.size();
+	if (!nd || !sg->n_c) {
+		return 0;
+	}
+	bytes.resize(bytes.size() + 16);
+	uint32_t chunk = std::min<uint32_t>(nd, 1u << 20);
+	bool full = false;
+	for (uint32_t c0 = 0; c0 < nd; ) {
+		const uint32_t nc = std::min(chunk, nd - c0);
+		const int r = sg_pass(ix, bytes.data(), off.data() + c0, nc, full, maxdist, k, dest.data() + c0,
+		    term_ids, dist, df, counts, matches);
+		if (r < 0) {
+			return -1;
+		}
+		if (r == 1) {
+			/* never a wrong answer: the same tokens again, fewer at a time; one token alone gets
+			 * queues that hold whatever the screen can emit */
+			if (nc > 1) {
+				chunk = std::max<uint32_t>(1, nc / 4);
+			} else if (!full) {
+				full = true;
+			} else {
+				set_error("suggest queue overflow (internal error)");
+				return -1;
+			}
+			continue;
+		}
+		full = false;
+		c0 += nc;
+	}
+	return 0;
+}
+
+extern "C" void
+nxsgpu_suggest_profile(nxsgpu_index_t *ix, double out[NXSGPU_SUGGEST_PROF], int reset)
+{
+	memset(out, 0, sizeof(double) * NXSGPU_SUGGEST_PROF);
+	if (ix->sg) {
+		memcpy(out, ix->sg->prof, sizeof(ix->sg->prof));
+		if (reset) {
+			memset(ix->sg->prof, 0, sizeof(ix->sg->prof));
+		}
+	}
+}

@@ -26,7 +26,8 @@
  *  nxs_gpu_wide.hip       k_scanw: queries beyond the fixed-size plan
  *  nxs_gpu_count.hip      k_count_tile / k_count_req: total match counts from the doc
  *                         ordinals of the primary CSR (no impacts, no heap)
- *  nxs_gpu_fuzzy.hip      BK-tree search (bktree.c:219-275) + Levenshtein
+ *  nxs_gpu_fuzzy.hip      BK-tree search (bktree.c:219-275) + Levenshtein; spelling
+ *                         suggestions over the same screen (k_sg_dist, k_sg_select)
  *  nxs_gpu_plan.hip       host only: query classes, the work list (build_worklist) and
  *                         the layout of a batch's arrays (batch_layout)
  *  nxs_gpu_search.hip     kernel dispatch, blocking search, batches in flight
@@ -173,6 +174,7 @@ struct gpu_cfg_t {
 	bool		use_scanb;	/* !NXS_GPU_NOSCANB: the mask path's sparsest queries on the presence-bit kernel (k_scanb) */
 	double		scanb_dens;	/* NXS_GPU_SCANB_DENS: ... those whose lists together hold at most this fraction of the docs */
 	uint32_t	count_mode;	/* NXS_GPU_COUNT=auto|tile|req|scan (COUNT_*): which kernel counts a query's matches */
+	bool		suggest_host;	/* NXS_GPU_SUGGEST=host: every suggestion from the host ranker (nxs_suggest.h): the cross-check */
 };
 enum : uint32_t { COUNT_AUTO = 0, COUNT_TILE = 1, COUNT_REQ = 2, COUNT_SCAN = 3 };
 
@@ -375,6 +377,15 @@ struct nxsgpu_index {
 	hipStream_t	stream_cnt;
 	count_buf_t	cnt_blk;
 	double		cnt_prof[6];	/* nxsgpu_count_profile */
+
+	/*
+	 * Spelling suggestions (nxsgpu_suggest, nxs_gpu_fuzzy.hip).  Nothing here exists until the first call.
+	 * The candidate permutation -- nodes with live postings, whatever the BK walk would reach -- is
+	 * built for generation sg_gen and rebuilt when a refresh, a new BK image or a collection-wide df
+	 * has bumped it since; the pass has a stream, workspace, staging and events of its own.
+	 */
+	struct sg_state_t *sg;
+	uint64_t	sg_gen;
 };
 
 static inline uint32_t __device__ __host__
@@ -598,6 +609,8 @@ void	pick_record_stream(nxsgpu_index_t *ix);
 /* ---- nxs_gpu_fuzzy.hip ---- */
 void	bk_aux_free(nxsgpu_index_t *ix);
 int	bk_aux_build(nxsgpu_index_t *ix, const nxsgpu_bknode_t *nodes, uint32_t n);
+
+void	sg_free(nxsgpu_index_t *ix);		/* everything nxsgpu_suggest has built (index destroy) */
 
 /* ---- nxs_gpu_plan.hip ---- */
 void	delete_worklist(worklist_t *);

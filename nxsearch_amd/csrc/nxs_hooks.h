@@ -72,6 +72,16 @@ uint64_t	nxs_test_impact_passes(nxs_index_t *);
 /* total match counts: docs per LDS tile of k_count_tile -- out[0] byte masks (<= 8 tokens), out[1] word masks
  * (tests straddle them) */
 void		nxs_test_count_tile_widths(uint32_t out[2]);
+/* spelling suggestions: the host ranker (nxs_suggest.h) over a dictionary handed in (term i has id i + 1;
+ * out_*: room for k), the parameters as nxs_index_suggest reads them (0, or -1 with the error declared), and
+ * an nxs_sugg_t built by hand (accessors and JSON without an index) */
+void		nxs_test_suggest_host(const uint8_t *const *terms, const uint32_t *lens, const uint32_t *dfs,
+		    uint32_t n_terms, const uint8_t *token, size_t len, uint32_t maxdist, uint32_t k,
+		    uint32_t *out_ids, uint8_t *out_dist, uint32_t *out_df, uint32_t *count, uint32_t *matches);
+int		nxs_test_suggest_params(nxs_t *, nxs_params_t *, unsigned *k, unsigned *maxdist);
+nxs_sugg_t *	nxs_test_sugg_build(const char *token, size_t token_len, bool dropped, uint64_t matches,
+		    unsigned count, const uint8_t *const *terms, const size_t *lens, const unsigned *dists,
+		    const uint64_t *dfs);
 
 #endif /* NXS_TEST_HOOKS */
 #endif /* NXS_HOOKS_H */
