@@ -46,8 +46,8 @@ typedef enum {
 
 nxs_err_t	nxs_get_error(const nxs_t *, const char **);	/* nxs.h:48 */
 
-/* Parameters (nxs.h:54-67); the query path reads limit / algo / fuzzymatch / total,
- * nxs_index_suggest reads suggest_limit / suggest_maxdist */
+/* Parameters (nxs.h:54-67); the query path reads limit / algo / fuzzymatch / total / prefixmatch /
+ * prefix_limit, nxs_index_suggest reads suggest_limit / suggest_maxdist, nxs_index_complete complete_limit */
 struct nxs_params;
 typedef struct nxs_params nxs_params_t;
 
@@ -158,6 +158,52 @@ bool		nxs_sugg_get(const nxs_sugg_t *, unsigned i, const char **term, size_t *le
 		    unsigned *distance, uint64_t *df);
 char *		nxs_sugg_tojson(nxs_sugg_t *, size_t *);
 void		nxs_sugg_release(nxs_sugg_t *);
+
+/*
+ * Prefix matching (new; the reference's lexer takes `*` for an ordinary byte of a free-form string,
+ * scan.re:76, so `micro*` is looked up verbatim there).
+ *
+ * The ELIGIBLE terms of a non-empty prefix p are the dictionary terms that have a posting in a live doc of
+ * the current snapshot (df > 0, the rule of the suggestions) and whose first len(p) bytes equal p; the term
+ * equal to p is eligible.  Their ORDER is df descending, then term id ascending: a total order.  A prefix is
+ * a fragment, not a word: it takes the normalizer / lowercase stage of the index's pipeline only -- no stop
+ * words (`th*` must not vanish), no stemmer.  On an index with the stemmer filter the dictionary holds
+ * STEMS, so the completions are stems.
+ *
+ * nxs_index_complete: the first min(k, matches) eligible terms of `prefix`, k = "complete_limit" (uint,
+ * 1..NXS_SUGGEST_MAX, default 5; out of range: NXS_ERR_INVALID naming the key), as an nxs_sugg_t read
+ * through the accessors above: nxs_sugg_get reports distance = len(term) - len(p), the pair's true
+ * Levenshtein distance; nxs_sugg_matches is the exact number of eligible terms; nxs_sugg_dropped is false.
+ * A prefix that is empty before or after normalisation is NXS_ERR_INVALID "empty prefix".
+ * nxs_sugg_tojson of such an object:
+ *   {"prefix":"<normalised prefix>","completions":[{"term":"...","df":12},...],"matches":7}
+ * with the escaping rules above.  nxs_index_complete_batch: as nxs_index_suggest_batch.  Everything else is
+ * nxs_index_suggest's: the call re-syncs with the files as a search does, is allowed while batches (or a
+ * batch's pending fuzzy pass) are in flight and neither finishes nor reorders them, is local under a
+ * communicator, and on a handle from nxs_index_open_shard fails with NXS_ERR_INVALID "complete is not
+ * available on a doc shard".
+ *
+ * Prefix leaves in queries: "prefixmatch" (bool, default FALSE) and "prefix_limit" (uint, 1..32, default 8;
+ * out of range: NXS_ERR_INVALID naming the key).  With prefixmatch false or absent nothing changes: `micro*`
+ * is the free-form string it always was.  With it, a leaf that comes from a free-form (not a quoted) string
+ * and ends in `*` with at least one byte in front of it is a prefix leaf: the star goes, the rest is
+ * normalised to p, and the query behaves EXACTLY as the query in which that leaf is the sub-expression
+ * (e1 OR e2 OR ... OR em), e1..em the first min(prefix_limit, matches) eligible terms of p in the order above,
+ * each an already resolved term (no filters, no fuzzy lookup): the doc set, the token set and its order
+ * (hence the float summation order and the ties), duplicates merged with the query's other tokens, and
+ * "total".  m = 0 makes the leaf the empty set.  A prefix leaf is never fuzzy-matched; the other leaves are,
+ * as always.  A lone `*` and a quoted "micro*" are ordinary leaves.  The expansions count towards the
+ * existing limits (truth table up to 8 live tokens, the wide plan above 32, NXS_ERR_LIMIT beyond that).
+ * Served by nxs_index_search, nxs_index_search_batch[_begin/_end] (any mix of batches in flight; the batch's
+ * distinct prefixes are resolved by one blocking device pass in _begin), nxs_index_plan_batch and
+ * query-sharded batches (the replicas hold the same dictionary and df: every rank derives the same
+ * expansions).  The nxs_docshard_* searches refuse a batch that holds a prefix leaf: -1 and NXS_ERR_INVALID
+ * "prefixmatch is not available on a doc shard".
+ */
+nxs_sugg_t *	nxs_index_complete(nxs_index_t *, nxs_params_t *, const char *prefix, size_t len);
+int		nxs_index_complete_batch(nxs_index_t *, nxs_params_t *,
+		    const char *const *prefixes, size_t n,
+		    nxs_sugg_t **out, nxs_err_t *errs);
 
 /*
  * Batch entry point (new).  Runs `n` queries with one set of params as one

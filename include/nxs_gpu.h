@@ -22,6 +22,9 @@
  *                           (src/algo/levdist.c:67-150).
  *   nxsgpu_suggest       (new: no seam in the reference) every term near a
  *                           token, ranked -- the same screen and distance.
+ *   nxsgpu_complete      (new: no seam in the reference) every live term that
+ *                           begins with a prefix, ranked by df -- a range of
+ *                           the terms' byte order.
  */
 #ifndef NXS_GPU_H
 #define NXS_GPU_H
@@ -319,6 +322,34 @@ int		nxsgpu_suggest(nxsgpu_index_t *, const uint8_t *tok_bytes, const uint32_t *
 		    uint32_t n_tokens, uint32_t maxdist, uint32_t k,
 		    uint32_t *term_ids, uint8_t *dist, uint32_t *df, uint32_t *counts, uint32_t *matches);
 void		nxsgpu_suggest_profile(nxsgpu_index_t *, double out[NXSGPU_SUGGEST_PROF], int reset);
+
+/*
+ * ---- prefix completion --------------------------------------------------------------
+ *
+ * nxsgpu_complete: for each of n prefixes (bytes off[i] .. off[i + 1], already normalised) the ELIGIBLE terms
+ * -- a posting in a live doc (df > 0, what nxsgpu_index_df reports) and the first len(p) bytes equal to p, the
+ * term equal to p included -- in the order df descending, term id ascending.  Rows of k (1..32) entries:
+ * term_ids / df [n][k], counts[i] = min(k, matches[i]) entries of row i are valid, matches[i] is the exact
+ * number of eligible terms.  An empty prefix matches every live term.
+ *
+ * The live terms of every length are kept in byte-lexicographic order on the device (one stable radix sort
+ * per 8-byte chunk, last chunk first), each with its (df, term id) beside it; a prefix is then two binary
+ * searches (k_px_range: the range's length IS the match count) and a selection over the range
+ * (k_px_select, one workgroup per prefix).  The order is built by the first call and rebuilt after
+ * nxsgpu_index_apply / _set_bk / _set_global_df (a generation counter: an index that is never asked builds,
+ * uploads and launches nothing).  The pass runs on a stream and workspace of its own: allowed while batches
+ * and fuzzy passes are in flight, takes none of their slots; blocking.  Under NXS_GPU_COMPLETE=host (the
+ * cross-check route) every prefix is ranked on the host over a copy of the BK image.  0 / -1.
+ *
+ * nxsgpu_complete_profile: since the last reset -- out[0] device passes, out[1] their HIP-event ms, out[2]
+ * k_px_range, out[3] k_px_select (out[0..3] with nxsgpu_set_profiling only), out[4] wall ms of the last build
+ * of the order (or of the host copy), out[5] entries in it, out[6] prefixes answered on the host, out[7]
+ * builds of the order.
+ */
+#define	NXSGPU_COMPLETE_PROF	8
+int		nxsgpu_complete(nxsgpu_index_t *, const uint8_t *bytes, const uint32_t *off, uint32_t n, uint32_t k,
+		    uint32_t *term_ids, uint32_t *df, uint32_t *counts, uint32_t *matches);	/* rows [n][k]; 0 / -1 */
+void		nxsgpu_complete_profile(nxsgpu_index_t *, double out[NXSGPU_COMPLETE_PROF], int reset);
 
 /*
  * ---- host batches as fixed-size records; query sharding over several GPUs ----

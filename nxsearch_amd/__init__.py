@@ -91,11 +91,14 @@ NXS_H_SYMBOLS = [
     "nxs_docshard_refresh", "nxs_docshard_refresh_rank", "nxs_resp_total",
     "nxs_index_suggest", "nxs_index_suggest_batch", "nxs_sugg_count", "nxs_sugg_matches", "nxs_sugg_dropped",
     "nxs_sugg_get", "nxs_sugg_tojson", "nxs_sugg_release",
+    "nxs_index_complete", "nxs_index_complete_batch",
 ]
 # csrc/nxs_hooks.h: test hooks + bench accessors, only in builds with -DNXS_TEST_HOOKS (the default)
 NXS_HOOK_SYMBOLS = ["nxs_index_device", "nxs_index_host_profile", "nxs_index_shard_info", "nxs_test_pool", "nxs_test_assemble",
                     "nxs_test_fixup_scan", "nxs_test_inject_failure", "nxs_test_count_tile_widths",
-                    "nxs_test_suggest_host", "nxs_test_suggest_params", "nxs_test_sugg_build"]
+                    "nxs_test_suggest_host", "nxs_test_suggest_params", "nxs_test_sugg_build",
+                    "nxs_test_complete_host", "nxs_test_complete_params", "nxs_test_compl_build",
+                    "nxs_test_prefix_query", "nxs_test_filter_prefix"]
 NXS_GPU_H_SYMBOLS = [
     "nxsgpu_device_count", "nxsgpu_last_error", "nxsgpu_index_create",
     "nxsgpu_index_destroy", "nxsgpu_index_df", "nxsgpu_index_postings",
@@ -114,6 +117,7 @@ NXS_GPU_H_SYMBOLS = [
     "nxsgpu_count", "nxsgpu_count_wide", "nxsgpu_search_totals", "nxsgpu_search_wide_totals", "nxsgpu_batch_begin_opts",
     "nxsgpu_batch_end_totals", "nxsgpu_count_tile_widths", "nxsgpu_count_profile",
     "nxsgpu_suggest", "nxsgpu_suggest_profile",
+    "nxsgpu_complete", "nxsgpu_complete_profile",
 ]
 
 _lib = None
@@ -189,6 +193,10 @@ def lib():
     L.nxs_index_suggest.argtypes = [vp, vp, cp, C.c_size_t]
     L.nxs_index_suggest_batch.restype = C.c_int
     L.nxs_index_suggest_batch.argtypes = [vp, vp, C.POINTER(cp), C.c_size_t, C.POINTER(vp), C.POINTER(C.c_int)]
+    L.nxs_index_complete.restype = vp
+    L.nxs_index_complete.argtypes = [vp, vp, cp, C.c_size_t]
+    L.nxs_index_complete_batch.restype = C.c_int
+    L.nxs_index_complete_batch.argtypes = [vp, vp, C.POINTER(cp), C.c_size_t, C.POINTER(vp), C.POINTER(C.c_int)]
     L.nxs_sugg_count.restype = C.c_uint
     L.nxs_sugg_count.argtypes = [vp]
     L.nxs_sugg_matches.restype = C.c_uint64
@@ -244,6 +252,12 @@ def lib():
                                  C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32),
                                  C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.nxsgpu_suggest_profile.argtypes = [vp, C.POINTER(C.c_double), C.c_int]
+    L.nxsgpu_complete.restype = C.c_int
+    L.nxsgpu_complete.argtypes = [vp, cp, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32,
+                                  C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                  C.POINTER(C.c_uint32)]
+    L.nxsgpu_complete_profile.restype = None
+    L.nxsgpu_complete_profile.argtypes = [vp, C.POINTER(C.c_double), C.c_int]
     # host-only test hooks
     L.nxs_test_query_repr.restype = vp
     L.nxs_test_query_repr.argtypes = [cp, C.POINTER(vp)]
@@ -324,9 +338,11 @@ class Nxs:
             self._raise()
         return Index(self, h)
 
-    def docshard_search_batch(self, shards, queries, limit=None, algo=None, fuzzymatch=None, total=False):
+    def docshard_search_batch(self, shards, queries, limit=None, algo=None, fuzzymatch=None, total=False,
+                              prefixmatch=None):
         """nxs_docshard_search_batch(): one batch over all shards, merged exactly.
-        total: every result list also carries `.total` (the sum of the shards' counts)."""
+        total: every result list also carries `.total` (the sum of the shards' counts).
+        (prefixmatch: a batch with a prefix leaf is refused -- NXS_ERR_INVALID.)"""
         L = lib()
         L.nxs_docshard_search_batch.restype = C.c_int
         L.nxs_docshard_search_batch.argtypes = [C.POINTER(C.c_void_p), C.c_uint, C.c_void_p,
@@ -337,7 +353,7 @@ class Nxs:
         qs = (C.c_char_p * max(n, 1))(*[_b(q) for q in queries])
         resps = (C.c_void_p * max(n, 1))()
         errs = (C.c_int * max(n, 1))()
-        p = _make_params(limit, algo, fuzzymatch, total)
+        p = _make_params(limit, algo, fuzzymatch, total, prefixmatch)
         try:
             r = L.nxs_docshard_search_batch(hs, len(shards), p, qs, n, resps, errs)
         finally:
@@ -553,8 +569,9 @@ def _suggest_params(limit=None, maxdist=None):
     return p
 
 
-def _make_params(limit=None, algo=None, fuzzymatch=None, total=False):
-    if limit is None and algo is None and fuzzymatch is None and not total:
+def _make_params(limit=None, algo=None, fuzzymatch=None, total=False, prefixmatch=None, prefix_limit=None):
+    if limit is None and algo is None and fuzzymatch is None and not total and prefixmatch is None \
+            and prefix_limit is None:
         return None
     L = lib()
     p = L.nxs_params_create()
@@ -566,6 +583,10 @@ def _make_params(limit=None, algo=None, fuzzymatch=None, total=False):
         L.nxs_params_set_bool(p, b"fuzzymatch", bool(fuzzymatch))
     if total:
         L.nxs_params_set_bool(p, b"total", True)
+    if prefixmatch is not None:
+        L.nxs_params_set_bool(p, b"prefixmatch", bool(prefixmatch))
+    if prefix_limit is not None:
+        L.nxs_params_set_uint(p, b"prefix_limit", prefix_limit)
     return p
 
 
@@ -595,10 +616,13 @@ class Index:
     def device(self):
         return lib().nxs_index_device(self._h)
 
-    def search(self, query, limit=None, algo=None, fuzzymatch=None, json=False, params_json=None, total=False):
+    def search(self, query, limit=None, algo=None, fuzzymatch=None, json=False, params_json=None, total=False,
+               prefixmatch=None, prefix_limit=None):
         """nxs_index_search(): -> [(doc_id, score), ...] (or the JSON text).
         params_json: the parameters as the Lua binding passes them (nxs_params_fromjson).
-        total: also count the matches -- the list then carries `.total` (the JSON a "total" member)."""
+        total: also count the matches -- the list then carries `.total` (the JSON a "total" member).
+        prefixmatch: a free-form leaf `term*` stands for the OR of its `prefix_limit` (1..32, default 8) best
+        completions."""
         L = lib()
         if params_json is not None:
             pj = _b(params_json)
@@ -606,7 +630,7 @@ class Index:
             if not p:
                 self.nxs._raise()
         else:
-            p = _make_params(limit, algo, fuzzymatch, total)
+            p = _make_params(limit, algo, fuzzymatch, total, prefixmatch, prefix_limit)
         q = _b(query)
         try:
             resp = L.nxs_index_search(self._h, p, q, len(q))
@@ -623,7 +647,8 @@ class Index:
         finally:
             L.nxs_resp_release(resp)
 
-    def search_batch(self, queries, limit=None, algo=None, fuzzymatch=None, total=False):
+    def search_batch(self, queries, limit=None, algo=None, fuzzymatch=None, total=False,
+                     prefixmatch=None, prefix_limit=None):
         """nxs_index_search_batch(): list of result lists; a failed query
         yields an NxsError instance in its slot.  total: every list carries `.total`."""
         L = lib()
@@ -631,7 +656,7 @@ class Index:
         qs = (C.c_char_p * n)(*[_b(q) for q in queries])
         resps = (C.c_void_p * n)()
         errs = (C.c_int * n)()
-        p = _make_params(limit, algo, fuzzymatch, total)
+        p = _make_params(limit, algo, fuzzymatch, total, prefixmatch, prefix_limit)
         try:
             r = L.nxs_index_search_batch(self._h, p, qs, n, resps, errs)
         finally:
@@ -648,13 +673,14 @@ class Index:
                 out.append(NxsError(errs[i], "query %d failed" % i))
         return out
 
-    def search_batch_begin(self, queries, limit=None, algo=None, fuzzymatch=None, total=False):
+    def search_batch_begin(self, queries, limit=None, algo=None, fuzzymatch=None, total=False,
+                           prefixmatch=None, prefix_limit=None):
         """nxs_index_search_batch_begin(): queue a batch (at most NXS_BATCHES_INFLIGHT = 4 in flight).
         total: the lists search_batch_end() returns for this batch carry `.total`."""
         L = lib()
         n = len(queries)
         qs = (C.c_char_p * max(n, 1))(*[_b(q) for q in queries])
-        p = _make_params(limit, algo, fuzzymatch, total)
+        p = _make_params(limit, algo, fuzzymatch, total, prefixmatch, prefix_limit)
         try:
             r = L.nxs_index_search_batch_begin(self._h, p, qs, n)
         finally:
@@ -732,14 +758,14 @@ class Index:
         """Re-read the NXS_GPU_* switches (parsed once at open); tests/tools."""
         lib().nxsgpu_index_reconfigure(self.device)
 
-    def plan_batch(self, queries, limit=None, algo=None, fuzzymatch=None):
+    def plan_batch(self, queries, limit=None, algo=None, fuzzymatch=None, prefixmatch=None, prefix_limit=None):
         """nxs_index_plan_batch(): -> (ctypes array of GpuQuery, [err codes])."""
         L = lib()
         n = len(queries)
         qs = (C.c_char_p * n)(*[_b(q) for q in queries])
         plans = (GpuQuery * max(n, 1))()
         errs = (C.c_int * max(n, 1))()
-        p = _make_params(limit, algo, fuzzymatch)
+        p = _make_params(limit, algo, fuzzymatch, False, prefixmatch, prefix_limit)
         try:
             r = L.nxs_index_plan_batch(self._h, p, qs, n, plans, errs)
         finally:
@@ -820,6 +846,38 @@ class Index:
         return {"passes": int(out[0]), "ms": out[1], "screen_ms": out[2], "dist_ms": out[3], "group_ms": out[4],
                 "select_ms": out[5], "survivors": int(out[6]), "matches": int(out[7]), "host_tokens": int(out[8]),
                 "overflow_reruns": int(out[9])}
+
+    def complete(self, prefixes, limit=None, json=False):
+        """nxs_index_complete_batch(): for every prefix (normalised, never stemmed or dropped as a stop word)
+        the dictionary terms that begin with it and that some live doc holds, best `limit` (1..32, default 5)
+        by df descending, then term id -> a list of Suggestions, one per prefix, entries (term, distance =
+        len(term) - len(prefix), df), `.matches` exact (an NxsError instance in the slot of a prefix that
+        failed: an empty one); json: their JSON texts."""
+        L = lib()
+        n = len(prefixes)
+        ps = (C.c_char_p * max(n, 1))(*[_b(t) for t in prefixes])
+        out = (C.c_void_p * max(n, 1))()
+        errs = (C.c_int * max(n, 1))()
+        p = None
+        if limit is not None:
+            p = L.nxs_params_create()
+            L.nxs_params_set_uint(p, b"complete_limit", limit)
+        try:
+            r = L.nxs_index_complete_batch(self._h, p, ps, n, out, errs)
+        finally:
+            if p:
+                L.nxs_params_release(p)
+        if r < 0:
+            self.nxs._raise()
+        return [_drain_sugg(out[i], json) if out[i] else NxsError(errs[i], "prefix %d failed" % i) for i in range(n)]
+
+    def complete_profile(self, reset=False):
+        """nxsgpu_complete_profile(): HIP-event times of the completion pass per kernel (profiling on), the
+        last build of the term order, its entries, prefixes answered on the host and order builds."""
+        out = (C.c_double * 8)()
+        lib().nxsgpu_complete_profile(self.device, out, 1 if reset else 0)
+        return {"passes": int(out[0]), "ms": out[1], "range_ms": out[2], "select_ms": out[3], "build_ms": out[4],
+                "entries": int(out[5]), "host_prefixes": int(out[6]), "builds": int(out[7])}
 
     def set_plan_cache(self, on=True):
         """bench: the index's plan cache (query string -> compiled plan) on / off."""

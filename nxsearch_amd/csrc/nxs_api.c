@@ -28,6 +28,7 @@
 #include "nxs_impl.h"
 #include "nxs_hooks.h"
 #include "nxs_suggest.h"
+#include "nxs_complete.h"
 
 struct plan_cache;
 static void plan_cache_destroy(struct plan_cache *);
@@ -1392,6 +1393,8 @@ typedef struct {
 	int		algo;
 	bool		fuzzymatch;
 	bool		total;		/* "total": also count the matches (nxs_resp_total) */
+	bool		prefixmatch;	/* "prefixmatch": a free-form leaf `term*` stands for its best completions */
+	unsigned	prefix_limit;	/* "prefix_limit": how many of them (1..NXS_PREFIX_MAX, default 8) */
 } search_params_t;
 
 /* get_search_params: search.c:78-112 */
@@ -1399,11 +1402,14 @@ static int
 get_search_params(nxs_index_t *idx, nxs_params_t *params, search_params_t *sp)
 {
 	const char *s;
+	uint64_t v;
 	bool fl;
 
 	sp->limit = NXS_DEFAULT_RESULTS_LIMIT;
 	sp->fuzzymatch = true;
 	sp->total = false;
+	sp->prefixmatch = false;
+	sp->prefix_limit = 8;
 	sp->algo = idx->algo;
 	if (!params) {
 		return 0;
@@ -1424,6 +1430,16 @@ get_search_params(nxs_index_t *idx, nxs_params_t *params, search_params_t *sp)
 	if (nxs_params_get_bool(params, "total", &fl) == 0 && fl) {
 		sp->total = true;
 	}
+	if (nxs_params_get_bool(params, "prefixmatch", &fl) == 0 && fl) {
+		sp->prefixmatch = true;
+	}
+	if (nxs_params_get_uint(params, "prefix_limit", &v) == 0) {
+		if (v < 1 || v > NXS_PREFIX_MAX) {
+			nxs_decl_err(idx->nxs, NXS_ERR_INVALID, "invalid prefix_limit (1..%d)", NXS_PREFIX_MAX);
+			return -1;
+		}
+		sp->prefix_limit = (unsigned)v;
+	}
 	return 0;
 }
 
@@ -1437,6 +1453,8 @@ get_search_params(nxs_index_t *idx, nxs_params_t *params, search_params_t *sp)
  * 60 % of a 1024-query step).  Lookups run on the worker threads (read-only); the batch's
  * misses are inserted by the caller's thread afterwards.  Only plans that fit
  * nxsgpu_query_t and queries without errors are kept.  NXS_PLAN_CACHE=0 turns it off.
+ * Under "prefixmatch" a string that holds a `*` bypasses the cache: what a prefix leaf stands for depends
+ * on prefix_limit and on the df of the moment, and the same string means something else with the flag off.
  */
 typedef struct {
 	uint64_t	h;
@@ -1600,7 +1618,7 @@ plan_parse_chunk(void *arg, size_t lo, size_t hi)
 	for (size_t i = lo; i < hi; i++) {
 		qprep_t *q = &j->prep[i];
 
-		if (j->pc) {
+		if (j->pc && !(j->sp->prefixmatch && strchr(j->queries[i], '*'))) {
 			const pc_ent_t *e = plan_cache_find(j->pc, j->queries[i], strlen(j->queries[i]), j->sp->fuzzymatch);
 			if (e) {
 				memset(q, 0, sizeof(*q));
@@ -1610,7 +1628,7 @@ plan_parse_chunk(void *arg, size_t lo, size_t hi)
 				continue;
 			}
 		}
-		nxs_query_prepare(j->idx, j->queries[i], q);
+		nxs_query_prepare_px(j->idx, j->queries[i], j->sp->prefixmatch, q);
 		if (q->errcode) {
 			nxs_query_release_scratch(q);	/* (what the second pass would do for it) */
 			q->compiled = true;
@@ -1625,7 +1643,8 @@ plan_parse_chunk(void *arg, size_t lo, size_t hi)
 		}
 		/* nothing of this query waits for the fuzzy search: compile it here and now -- a batch without
 		 * misses (or with fuzzymatch off) is ONE run over the worker threads, not two */
-		if (!miss || !j->sp->fuzzymatch) {
+		/* (a query with prefix leaves waits for the batch's completion pass: plan_prefixes) */
+		if ((!miss || !j->sp->fuzzymatch) && !q->n_pfx) {
 			(void)nxs_query_compile(q);
 			nxs_query_release_scratch(q);
 			q->compiled = true;
@@ -1669,6 +1688,144 @@ fz_set_free(fz_set_t *fz)
 	memset(fz, 0, sizeof(*fz));
 }
 
+static int late_finish(nxs_index_t *);
+
+typedef struct { const char *val; size_t len; uint32_t q, k, slot; } pfx_ref_t;
+
+static int
+pfx_ref_cmp(const void *a, const void *b)
+{
+	const pfx_ref_t *x = a, *y = b;
+
+	if (x->len != y->len) {
+		return x->len < y->len ? -1 : 1;
+	}
+	return memcmp(x->val, y->val, x->len);
+}
+
+/*
+ * The prefix leaves of a batch: its distinct prefixes are resolved by ONE blocking completion pass
+ * (nxsgpu_complete, k = prefix_limit), each leaf's expansions are spliced into its query's program and token
+ * list (nxs_query_splice), and a query that waits for nothing else is compiled.  A batch without a prefix
+ * leaf makes no call.
+ */
+static int
+plan_prefixes(nxs_index_t *idx, const search_params_t *sp, size_t n, qprep_t *prep)
+{
+	nxs_t *nxs = idx->nxs;
+	const unsigned k = sp->prefix_limit;
+	size_t n_ref = 0, nd = 0, blen = 0, r = 0;
+	pfx_ref_t *ref = NULL;
+	uint8_t *bytes = NULL;
+	uint32_t *off = NULL, *ids = NULL, *df = NULL, *counts = NULL, *matches = NULL;
+	int ret = -1;
+
+	for (size_t i = 0; i < n; i++) {
+		n_ref += prep[i].errcode ? 0 : prep[i].n_pfx;
+	}
+	if (!n_ref) {
+		return 0;
+	}
+	/* (a shard's postings are its own: the df the order rests on would be the shard's; include/nxs.h) */
+	if (idx->n_shards) {
+		nxs_decl_err(nxs, NXS_ERR_INVALID, "prefixmatch is not available on a doc shard");
+		return -1;
+	}
+	if ((ref = malloc(n_ref * sizeof(*ref))) == NULL) {
+		nxs_decl_err(nxs, NXS_ERR_SYSTEM, "out of memory");
+		return -1;
+	}
+	for (size_t i = 0; i < n; i++) {
+		for (size_t j = 0; !prep[i].errcode && j < prep[i].n_pfx; j++) {
+			ref[r++] = (pfx_ref_t){ prep[i].pfx[j].val, prep[i].pfx[j].len, (uint32_t)i, (uint32_t)j, 0 };
+		}
+	}
+	qsort(ref, n_ref, sizeof(*ref), pfx_ref_cmp);
+	for (r = 0; r < n_ref; r++) {
+		if (r == 0 || pfx_ref_cmp(&ref[r - 1], &ref[r]) != 0) {
+			nd++;
+			blen += ref[r].len;
+		}
+		ref[r].slot = (uint32_t)(nd - 1);
+	}
+	bytes = malloc(blen + 16);
+	off = malloc((nd + 1) * sizeof(*off));
+	ids = malloc(nd * k * sizeof(*ids));
+	df = malloc(nd * k * sizeof(*df));
+	counts = malloc(nd * sizeof(*counts));
+	matches = malloc(nd * sizeof(*matches));
+	if (!bytes || !off || !ids || !df || !counts || !matches || blen > UINT32_MAX / 2) {
+		nxs_decl_err(nxs, NXS_ERR_SYSTEM, "out of memory");
+		goto out;
+	}
+	blen = 0;
+	for (r = 0; r < n_ref; r++) {
+		if (r == 0 || ref[r].slot != ref[r - 1].slot) {
+			off[ref[r].slot] = (uint32_t)blen;
+			memcpy(bytes + blen, ref[r].val, ref[r].len);
+			blen += ref[r].len;
+		}
+	}
+	off[nd] = (uint32_t)blen;
+	/* new terms reach the BK image first (as nxs_index_suggest: a batch whose fuzzy pass is still on the
+	 * device reads the image, so that pass is waited for before the image is replaced) */
+	if (idx->bk_upto != idx->last_id || idx->bk_flags_stale) {
+		(void)late_finish(idx);
+		if (nxs_index_bk_sync(idx) == -1) {
+			goto out;
+		}
+	}
+	if (nxsgpu_complete(idx->dev, bytes, off, (uint32_t)nd, k, ids, df, counts, matches) != 0) {
+		nxs_decl_err(nxs, NXS_ERR_FATAL, "device complete pass failed: %s", nxsgpu_last_error());
+		goto out;
+	}
+	for (r = 0; r < n_ref; r++) {
+		qpfx_t *px = &prep[ref[r].q].pfx[ref[r].k];
+		const uint32_t *row = ids + (size_t)ref[r].slot * k;
+
+		px->n = counts[ref[r].slot] <= k ? counts[ref[r].slot] : k;
+		for (uint32_t e = 0; e < px->n; e++) {
+			if (row[e] < 1 || row[e] > idx->last_id) {
+				nxs_decl_err(nxs, NXS_ERR_FATAL, "the device named an unknown term for a prefix");
+				goto out;
+			}
+			px->ids[e] = row[e];
+			px->tval[e] = idx->terms[row[e]].val;
+			px->tlen[e] = idx->terms[row[e]].len;
+		}
+	}
+	for (size_t i = 0; i < n; i++) {
+		qprep_t *q = &prep[i];
+		bool miss = false;
+
+		if (q->errcode || !q->n_pfx) {
+			continue;
+		}
+		if (nxs_query_splice(q) == -1) {
+			nxs_decl_err(nxs, NXS_ERR_SYSTEM, "out of memory");
+			goto out;
+		}
+		for (size_t j = 0; j < q->n_tokens; j++) {
+			miss = miss || !q->tokens[j].term_id;
+		}
+		if (!miss || !sp->fuzzymatch) {
+			(void)nxs_query_compile(q);
+			nxs_query_release_scratch(q);
+			q->compiled = true;
+		}
+	}
+	ret = 0;
+out:
+	free(ref);
+	free(bytes);
+	free(off);
+	free(ids);
+	free(df);
+	free(counts);
+	free(matches);
+	return ret;
+}
+
 /* parse + lookups (+ compile for the queries without misses) on the worker threads; the misses into *fz */
 static int
 plan_front(nxs_index_t *idx, const search_params_t *sp, const char *const *queries,
@@ -1681,6 +1838,9 @@ plan_front(nxs_index_t *idx, const search_params_t *sp, const char *const *queri
 
 	memset(fz, 0, sizeof(*fz));
 	pool_run(pool, plan_parse_chunk, &job, n, 16);
+	if (sp->prefixmatch && plan_prefixes(idx, sp, n, prep) == -1) {
+		return -1;
+	}
 
 	for (size_t i = 0; sp->fuzzymatch && i < n; i++) {
 		const qprep_t *q = &prep[i];
@@ -1751,13 +1911,11 @@ plan_back(nxs_index_t *idx, const search_params_t *sp, const char *const *querie
 	 * still has to compile -- was put there by the first half's caller or is not cached) */
 	for (size_t i = 0; pc && i < n; i++) {
 		const qprep_t *q = &prep[i];
-		if (queries[i] && !q->cached && !q->errcode && !q->wide) {
+		if (queries[i] && !q->cached && !q->errcode && !q->wide && !q->has_prefix) {
 			plan_cache_put(pc, queries[i], strlen(queries[i]), sp->fuzzymatch, q);
 		}
 	}
 }
-
-static int late_finish(nxs_index_t *);
 
 static int
 plan_batch(nxs_index_t *idx, const search_params_t *sp, const char *const *queries,
@@ -3124,6 +3282,7 @@ struct nxs_sugg {
 	char *		token;		/* the token after the filters (empty when dropped) */
 	size_t		token_len;
 	bool		dropped;
+	bool		completion;	/* built by nxs_index_complete: `token` is the prefix, the JSON has its own shape */
 	uint64_t	matches;
 	unsigned	count;
 	sugg_item_t	items[];
@@ -3151,6 +3310,7 @@ sugg_build(const char *token, size_t token_len, bool dropped, uint64_t matches, 
 	str[token_len] = '\0';
 	str += token_len + 1;
 	sg->dropped = dropped;
+	sg->completion = false;
 	sg->matches = matches;
 	sg->count = count;
 	for (unsigned i = 0; i < count; i++) {
@@ -3224,7 +3384,8 @@ json_str(char *out, const char *s, size_t n)
 	return o;
 }
 
-/* {"token":"...","suggestions":[{"term":"...","distance":D,"df":N},...],"matches":M} */
+/* {"token":"...","suggestions":[{"term":"...","distance":D,"df":N},...],"matches":M}; of a completion:
+ * {"prefix":"...","completions":[{"term":"...","df":N},...],"matches":M} */
 char *
 nxs_sugg_tojson(nxs_sugg_t *sg, size_t *len)
 {
@@ -3237,14 +3398,18 @@ nxs_sugg_tojson(nxs_sugg_t *sg, size_t *len)
 	if ((s = malloc(cap)) == NULL) {
 		return NULL;
 	}
-	o += (size_t)sprintf(s + o, "{\"token\":");
+	o += (size_t)sprintf(s + o, sg->completion ? "{\"prefix\":" : "{\"token\":");
 	o += json_str(s + o, sg->token, sg->token_len);
-	o += (size_t)sprintf(s + o, ",\"suggestions\":[");
+	o += (size_t)sprintf(s + o, sg->completion ? ",\"completions\":[" : ",\"suggestions\":[");
 	for (unsigned i = 0; i < sg->count; i++) {
 		o += (size_t)sprintf(s + o, "%s{\"term\":", i ? "," : "");
 		o += json_str(s + o, sg->items[i].term, sg->items[i].len);
-		o += (size_t)sprintf(s + o, ",\"distance\":%u,\"df\":%llu}", sg->items[i].dist,
-		    (unsigned long long)sg->items[i].df);
+		if (sg->completion) {
+			o += (size_t)sprintf(s + o, ",\"df\":%llu}", (unsigned long long)sg->items[i].df);
+		} else {
+			o += (size_t)sprintf(s + o, ",\"distance\":%u,\"df\":%llu}", sg->items[i].dist,
+			    (unsigned long long)sg->items[i].df);
+		}
 	}
 	o += (size_t)sprintf(s + o, "],\"matches\":%llu}", (unsigned long long)sg->matches);
 	if (len) {
@@ -3486,7 +3651,356 @@ nxs_index_suggest(nxs_index_t *idx, nxs_params_t *params, const char *token, siz
 	return sg;
 }
 
+/* ---- prefix completion (nxs_index_complete) ------------------------------------------- */
+
+/* "complete_limit" (1..NXS_SUGGEST_MAX, default 5) */
+static int
+get_complete_params(nxs_t *nxs, const nxs_params_t *params, unsigned *k)
+{
+	uint64_t v;
+
+	*k = 5;
+	if (params && nxs_params_get_uint(params, "complete_limit", &v) == 0) {
+		if (v < 1 || v > NXS_SUGGEST_MAX) {
+			nxs_decl_err(nxs, NXS_ERR_INVALID, "invalid complete_limit (1..%d)", NXS_SUGGEST_MAX);
+			return -1;
+		}
+		*k = (unsigned)v;
+	}
+	return 0;
+}
+
+/* lens: NULL = the strings are NUL-terminated */
+static int
+complete_core(nxs_index_t *idx, nxs_params_t *params, const char *const *prefixes, const size_t *lens, size_t n,
+    nxs_sugg_t **out, nxs_err_t *errs)
+{
+	nxs_t *nxs = idx->nxs;
+	unsigned k;
+	char **val = NULL;
+	size_t *vlen = NULL, blen = 0, nd = 0;
+	int8_t *act = NULL;
+	uint8_t *bytes = NULL;
+	uint32_t *off = NULL, *ids = NULL, *df = NULL, *counts = NULL, *matches = NULL;
+	int ret = -1, failed = 0;
+
+	nxs_clear_error(nxs);
+	for (size_t i = 0; i < n; i++) {
+		out[i] = NULL;
+		if (errs) {
+			errs[i] = NXS_ERR_SUCCESS;
+		}
+	}
+	if (get_complete_params(nxs, params, &k) == -1) {
+		return -1;
+	}
+	/* (a shard's dictionary and df are collection-wide, its postings are not: as nxs_index_suggest) */
+	if (idx->n_shards) {
+		nxs_decl_err(nxs, NXS_ERR_INVALID, "complete is not available on a doc shard");
+		return -1;
+	}
+	if (n > UINT32_MAX / 2) {
+		nxs_decl_err(nxs, NXS_ERR_LIMIT, "batch too large");
+		return -1;
+	}
+	/* search.c:309-312, as every search does; local under a communicator (suggest_core) */
+	if (!(idx->comm && pend_oldest(idx)) && resync_before_batch(idx) == -1) {
+		return -1;
+	}
+	if (idx->bk_upto != idx->last_id || idx->bk_flags_stale) {
+		(void)late_finish(idx);
+		if (nxs_index_bk_sync(idx) == -1) {
+			return -1;
+		}
+	}
+	val = calloc(n ? n : 1, sizeof(*val));
+	vlen = calloc(n ? n : 1, sizeof(*vlen));
+	act = calloc(n ? n : 1, sizeof(*act));
+	off = malloc((n + 1) * sizeof(*off));
+	if (!val || !vlen || !act || !off) {
+		nxs_decl_err(nxs, NXS_ERR_SYSTEM, "out of memory");
+		goto out;
+	}
+	/* a prefix is a fragment, not a word: the normalizer / lowercase stage only (nxs_filters_run_stages) */
+	for (size_t i = 0; i < n; i++) {
+		size_t len = lens ? lens[i] : strlen(prefixes[i]);
+
+		if ((val[i] = malloc(len + 1)) == NULL) {
+			nxs_decl_err(nxs, NXS_ERR_SYSTEM, "out of memory");
+			goto out;
+		}
+		memcpy(val[i], prefixes[i], len);
+		val[i][len] = '\0';
+		act[i] = 1;
+		if (idx->filters) {
+			act[i] = (int8_t)nxs_filters_run_stages(idx->filters, NXS_FSTAGE_NORMALIZER, &val[i], &len);
+		} else if (idx->lowercase) {
+			for (size_t c = 0; c < len; c++) {
+				if (val[i][c] >= 'A' && val[i][c] <= 'Z') {
+					val[i][c] += 32;
+				}
+			}
+		}
+		vlen[i] = len;
+		if (act[i] == 1 && len == 0) {
+			act[i] = 0;		/* empty before or after normalisation: NXS_ERR_INVALID below */
+		}
+		if (act[i] == 1) {
+			blen += len;
+			nd++;
+		}
+	}
+	if (blen > UINT32_MAX / 2) {
+		nxs_decl_err(nxs, NXS_ERR_LIMIT, "batch too large");
+		goto out;
+	}
+	bytes = malloc(blen + 16);
+	ids = malloc((nd * k + 1) * sizeof(*ids));
+	df = malloc((nd * k + 1) * sizeof(*df));
+	counts = malloc((nd + 1) * sizeof(*counts));
+	matches = malloc((nd + 1) * sizeof(*matches));
+	if (!bytes || !ids || !df || !counts || !matches) {
+		nxs_decl_err(nxs, NXS_ERR_SYSTEM, "out of memory");
+		goto out;
+	}
+	blen = 0;
+	nd = 0;
+	for (size_t i = 0; i < n; i++) {
+		if (act[i] == 1) {
+			off[nd++] = (uint32_t)blen;
+			memcpy(bytes + blen, val[i], vlen[i]);
+			blen += vlen[i];
+		}
+	}
+	off[nd] = (uint32_t)blen;
+	if (nd && nxsgpu_complete(idx->dev, bytes, off, (uint32_t)nd, k, ids, df, counts, matches) != 0) {
+		nxs_decl_err(nxs, NXS_ERR_FATAL, "device complete pass failed: %s", nxsgpu_last_error());
+		goto out;
+	}
+	nd = 0;
+	for (size_t i = 0; i < n; i++) {
+		const uint8_t *terms[NXS_SUGGEST_MAX];
+		size_t tlens[NXS_SUGGEST_MAX];
+		unsigned dists[NXS_SUGGEST_MAX];
+		uint64_t dfs[NXS_SUGGEST_MAX];
+
+		if (act[i] < 0) {
+			if (errs) {
+				errs[i] = NXS_ERR_FATAL;
+			}
+			nxs_decl_err(nxs, NXS_ERR_FATAL, "the filters failed on prefix %zu", i);
+			failed++;
+			continue;
+		}
+		if (act[i] == 0) {
+			if (errs) {
+				errs[i] = NXS_ERR_INVALID;
+			}
+			nxs_decl_err(nxs, NXS_ERR_INVALID, "empty prefix");
+			failed++;
+			continue;
+		}
+		const unsigned c = counts[nd] <= k ? counts[nd] : k;
+		bool bad = false;
+
+		for (unsigned j = 0; j < c; j++) {
+			const uint32_t id = ids[nd * k + j];
+			if (id < 1 || id > idx->last_id || idx->terms[id].len < vlen[i]) {
+				bad = true;
+				break;
+			}
+			terms[j] = idx->terms[id].val;
+			tlens[j] = idx->terms[id].len;
+			dists[j] = (unsigned)(tlens[j] - vlen[i]);	/* the pair's true Levenshtein distance */
+			dfs[j] = df[nd * k + j];
+		}
+		if (bad) {
+			if (errs) {
+				errs[i] = NXS_ERR_FATAL;
+			}
+			nxs_decl_err(nxs, NXS_ERR_FATAL, "the device named an unknown term for prefix %zu", i);
+			failed++;
+			nd++;
+			continue;
+		}
+		out[i] = sugg_build(val[i], vlen[i], false, matches[nd], c, terms, tlens, dists, dfs);
+		nd++;
+		if (!out[i]) {
+			if (errs) {
+				errs[i] = NXS_ERR_SYSTEM;
+			}
+			nxs_decl_err(nxs, NXS_ERR_SYSTEM, "out of memory");
+			failed++;
+		} else {
+			out[i]->completion = true;
+		}
+	}
+	ret = failed;
+out:
+	for (size_t i = 0; val && i < n; i++) {
+		free(val[i]);
+	}
+	free(val);
+	free(vlen);
+	free(act);
+	free(off);
+	free(bytes);
+	free(ids);
+	free(df);
+	free(counts);
+	free(matches);
+	return ret;
+}
+
+int
+nxs_index_complete_batch(nxs_index_t *idx, nxs_params_t *params, const char *const *prefixes, size_t n,
+    nxs_sugg_t **out, nxs_err_t *errs)
+{
+	return complete_core(idx, params, prefixes, NULL, n, out, errs);
+}
+
+nxs_sugg_t *
+nxs_index_complete(nxs_index_t *idx, nxs_params_t *params, const char *prefix, size_t len)
+{
+	nxs_sugg_t *sg = NULL;
+	const char *pv[1] = { prefix };
+
+	if (complete_core(idx, params, pv, &len, 1, &sg, NULL) != 0) {
+		if (sg) {
+			nxs_sugg_release(sg);
+		}
+		return NULL;
+	}
+	return sg;
+}
+
 #ifdef NXS_TEST_HOOKS
+/* the host ranker of completions (nxs_complete.h) over a dictionary handed in: term i has id i + 1 */
+void
+nxs_test_complete_host(const uint8_t *const *terms, const uint32_t *lens, const uint32_t *dfs, uint32_t n_terms,
+    const uint8_t *prefix, size_t len, uint32_t k, uint32_t *out_ids, uint32_t *out_df, uint32_t *count,
+    uint32_t *matches)
+{
+	nxs_complete_rank(terms, lens, dfs, NULL, n_terms, prefix, len, k, out_ids, out_df, count, matches);
+}
+
+/* the parameters as nxs_index_complete / a search read them: 0, or -1 with the error declared */
+int
+nxs_test_complete_params(nxs_t *nxs, nxs_params_t *params, unsigned *k, int *prefixmatch, unsigned *prefix_limit)
+{
+	nxs_index_t fake = { .nxs = nxs };
+	search_params_t sp;
+
+	nxs_clear_error(nxs);
+	if (get_complete_params(nxs, params, k) == -1 || get_search_params(&fake, params, &sp) == -1) {
+		return -1;
+	}
+	*prefixmatch = sp.prefixmatch;
+	*prefix_limit = sp.prefix_limit;
+	return 0;
+}
+
+/* an nxs_sugg_t of the completion kind built by hand */
+nxs_sugg_t *
+nxs_test_compl_build(const char *prefix, size_t prefix_len, uint64_t matches, unsigned count,
+    const uint8_t *const *terms, const size_t *lens, const uint64_t *dfs)
+{
+	unsigned dists[NXS_SUGGEST_MAX];
+	nxs_sugg_t *sg;
+
+	for (unsigned i = 0; i < count && i < NXS_SUGGEST_MAX; i++) {
+		dists[i] = (unsigned)(lens[i] - prefix_len);
+	}
+	if ((sg = sugg_build(prefix, prefix_len, false, matches, count, terms, lens, dists, dfs)) != NULL) {
+		sg->completion = true;
+	}
+	return sg;
+}
+
+/*
+ * A query with prefix leaves against a dictionary handed in (words[i]: term id i + 1, df dfs[i]): prepare
+ * (prefixmatch as given), resolve every prefix with the host ranker, splice.  -> the IR dump of the result
+ * (nxs_query_repr; NULL on error), *n_prefix = the leaves read as prefixes, `prefixes` = their normalised
+ * bytes in source order, one per line.
+ */
+char *
+nxs_test_prefix_query(const char *query, const char *const *words, const uint32_t *dfs, uint32_t n_words,
+    bool lowercase, bool prefixmatch, uint32_t prefix_limit, uint32_t *n_prefix, char *prefixes, size_t cap)
+{
+	nxs_index_t fake = { .lowercase = lowercase };
+	const uint8_t **terms = calloc(n_words + 1, sizeof(*terms));
+	uint32_t *lens = calloc(n_words + 1, sizeof(*lens));
+	char *repr = NULL;
+	size_t o = 0;
+	qprep_t q;
+
+	nxs_query_prepare_px(&fake, query, prefixmatch, &q);
+	*n_prefix = (uint32_t)q.n_pfx;
+	if (prefixes && cap) {
+		prefixes[0] = '\0';
+	}
+	for (uint32_t w = 0; terms && lens && w < n_words; w++) {
+		terms[w] = (const uint8_t *)words[w];
+		lens[w] = (uint32_t)strlen(words[w]);
+	}
+	if (!q.errcode && terms && lens) {
+		for (size_t i = q.n_pfx; i-- > 0; ) {
+			qpfx_t *px = &q.pfx[i];
+			uint32_t df[NXS_PREFIX_MAX], cnt = 0, m = 0;
+
+			if (prefixes && o + px->len + 2 <= cap) {
+				memcpy(prefixes + o, px->val, px->len);
+				o += px->len;
+				prefixes[o++] = '\n';
+				prefixes[o] = '\0';
+			}
+			nxs_complete_rank(terms, lens, dfs, NULL, n_words, (const uint8_t *)px->val, px->len,
+			    prefix_limit, px->ids, df, &cnt, &m);
+			px->n = cnt;
+			for (uint32_t e = 0; e < cnt; e++) {
+				px->tval[e] = terms[px->ids[e] - 1];
+				px->tlen[e] = (uint16_t)lens[px->ids[e] - 1];
+			}
+		}
+		if (nxs_query_splice(&q) == 0) {
+			repr = nxs_query_repr(&q.parse);
+		}
+	}
+	nxs_query_release(&q);
+	free(terms);
+	free(lens);
+	return repr;
+}
+
+/* the stages a PREFIX takes (the normalizer only) of a pipeline with stop words (bit 0 of `stages`) and the
+ * stemmer (bit 1), on one string -> malloc'd result, NULL on error (*act: nxs_filters_run_stages's) */
+char *
+nxs_test_filter_prefix(const char *basedir, int stages, const char *s, int *act)
+{
+	const char *names[3] = { "normalizer" };
+	size_t n = 1;
+	const char *err = NULL;
+	nxs_filters_t *f;
+	if (stages & 1) names[n++] = "stopwords";
+	if (stages & 2) names[n++] = "stemmer";
+	f = nxs_filters_create(basedir, names, n, "en", &err);
+	char *val = strdup(s);
+	size_t len = strlen(s);
+
+	*act = -2;
+	if (!f) {
+		free(val);
+		return NULL;
+	}
+	*act = nxs_filters_run_stages(f, NXS_FSTAGE_NORMALIZER, &val, &len);
+	nxs_filters_destroy(f);
+	if (*act != 1) {
+		free(val);
+		return NULL;
+	}
+	return val;
+}
+
 /* the host ranker (nxs_suggest.h) over a dictionary handed in: term i has id i + 1 */
 void
 nxs_test_suggest_host(const uint8_t *const *terms, const uint32_t *lens, const uint32_t *dfs, uint32_t n_terms,

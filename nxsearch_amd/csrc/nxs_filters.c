@@ -41,7 +41,7 @@
 
 #define	NORM_BUF_MULTI	3	/* utf8.c:33 */
 
-enum { F_NORMALIZER = 1, F_STOPWORDS = 2, F_STEMMER = 3 };
+enum { F_NORMALIZER = 1, F_STOPWORDS = 2, F_STEMMER = 3 };	/* (NXS_FSTAGE_* of nxs_impl.h: 1 << these) */
 
 struct nxs_filters {
 	unsigned		stage[4];
@@ -323,6 +323,49 @@ nxs_filters_run(nxs_filters_t *f, char **val, size_t *len)
 			}
 		} else if (f->stage[s] == F_STEMMER) {
 			/* stemmer_filter: filters_builtin.c:219-238 (in place: never longer) */
+			*len = nxs_stem_en(*val, *len);
+			(*val)[*len] = '\0';
+		}
+	}
+	return 1;
+}
+
+/*
+ * The same on a chosen subset of the pipeline's stages (NXS_FSTAGE_* bits): the stages of the index's list
+ * that are in `stages` run, in list order, the others are skipped.  A query PREFIX (nxs_index_complete, a
+ * `term*` leaf) is a fragment, not a word: it takes the normalizer only -- `th*` must not vanish as a stop
+ * word, and a stem of a fragment is not a prefix of the stems.
+ */
+int
+nxs_filters_run_stages(nxs_filters_t *f, unsigned stages, char **val, size_t *len)
+{
+	for (unsigned s = 0; f && s < f->n_stages; s++) {
+		if (!(stages & (1u << f->stage[s]))) {
+			continue;
+		}
+		if (f->stage[s] == F_NORMALIZER) {
+			bool ascii = true;
+
+			for (size_t i = 0; i < *len; i++) {
+				if ((unsigned char)(*val)[i] >= 0x80) {
+					ascii = false;
+					break;
+				}
+			}
+			if (ascii) {
+				for (size_t i = 0; i < *len; i++) {
+					if ((*val)[i] >= 'A' && (*val)[i] <= 'Z') {
+						(*val)[i] += 32;
+					}
+				}
+			} else if (normalize_icu(f, val, len) == -1) {
+				return -1;
+			}
+		} else if (f->stage[s] == F_STOPWORDS) {
+			if (sw_has(f, *val, *len)) {
+				return 0;
+			}
+		} else if (f->stage[s] == F_STEMMER) {
 			*len = nxs_stem_en(*val, *len);
 			(*val)[*len] = '\0';
 		}

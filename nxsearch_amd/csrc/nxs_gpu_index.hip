@@ -126,6 +126,10 @@ cfg_from_env(gpu_cfg_t &c)
 		const char *e = getenv("NXS_GPU_SUGGEST");
 		c.suggest_host = e && !strcmp(e, "host");
 	}
+	{
+		const char *e = getenv("NXS_GPU_COMPLETE");
+		c.complete_host = e && !strcmp(e, "host");
+	}
 }
 
 /* ------------------------------------------------------------------ */
@@ -653,6 +657,7 @@ nxsgpu_index_destroy(nxsgpu_index_t *ix)
 	(void)hipFree(ix->d_bk);
 	(void)hipFree(ix->d_bk_bytes);
 	sg_free(ix);
+	px_free(ix);
 	bk_aux_free(ix);
 	(void)hipFree(ix->ws);
 	(void)hipFree(ix->fz);
@@ -1550,6 +1555,7 @@ nxsgpu_index_apply(nxsgpu_index_t *ix, const nxsgpu_index_delta_t *d)
 	const double t_a0 = now_ms();
 	double t_a1 = t_a0, t_a2 = t_a0;
 	ix->sg_gen++;		/* (df changes: the suggest candidates are rebuilt by the next call that asks) */
+	ix->px_gen++;		/* (... and the completion order) */
 	if (nxsgpu_batches_in_flight(ix)) {
 		set_error("nxsgpu_index_apply: batches are in flight");
 		return -1;
@@ -1788,6 +1794,7 @@ nxsgpu_index_set_bk(nxsgpu_index_t *ix, const nxsgpu_bknode_t *nodes, uint32_t n
 		return -1;
 	}
 	ix->sg_gen++;
+	ix->px_gen++;
 	(void)hipStreamSynchronize(ix->stream_fz);
 	(void)hipFree(ix->d_bk);
 	(void)hipFree(ix->d_bk_bytes);
@@ -1879,6 +1886,7 @@ nxsgpu_index_set_global_df(nxsgpu_index_t *ix, const uint32_t *df, uint32_t n_te
 		return -1;
 	}
 	ix->sg_gen++;
+	ix->px_gen++;
 	ix->df_global.assign((size_t)n_terms + 2, 0);
 	for (uint32_t t = 1; t <= n_terms; t++) {
 		ix->df_global[t] = df[t];

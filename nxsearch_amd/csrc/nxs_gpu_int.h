@@ -28,6 +28,8 @@
  *                         ordinals of the primary CSR (no impacts, no heap)
  *  nxs_gpu_fuzzy.hip      BK-tree search (bktree.c:219-275) + Levenshtein; spelling
  *                         suggestions over the same screen (k_sg_dist, k_sg_select)
+ *  nxs_gpu_prefix.hip     prefix completion: the live terms in byte order (k_px_keys + radix sort), a
+ *                         range per prefix (k_px_range), its k best by df (k_px_select)
  *  nxs_gpu_plan.hip       host only: query classes, the work list (build_worklist) and
  *                         the layout of a batch's arrays (batch_layout)
  *  nxs_gpu_search.hip     kernel dispatch, blocking search, batches in flight
@@ -175,6 +177,7 @@ struct gpu_cfg_t {
 	double		scanb_dens;	/* NXS_GPU_SCANB_DENS: ... those whose lists together hold at most this fraction of the docs */
 	uint32_t	count_mode;	/* NXS_GPU_COUNT=auto|tile|req|scan (COUNT_*): which kernel counts a query's matches */
 	bool		suggest_host;	/* NXS_GPU_SUGGEST=host: every suggestion from the host ranker (nxs_suggest.h): the cross-check */
+	bool		complete_host;	/* NXS_GPU_COMPLETE=host: every completion from the host ranker (nxs_complete.h): the cross-check */
 };
 enum : uint32_t { COUNT_AUTO = 0, COUNT_TILE = 1, COUNT_REQ = 2, COUNT_SCAN = 3 };
 
@@ -386,6 +389,13 @@ struct nxsgpu_index {
 	 */
 	struct sg_state_t *sg;
 	uint64_t	sg_gen;
+	/*
+	 * Prefix completion (nxsgpu_complete, nxs_gpu_prefix.hip), on the same terms: nothing exists until the
+	 * first call; the byte order of the live terms is built for generation px_gen, which moves wherever
+	 * sg_gen does.
+	 */
+	struct px_state_t *px;
+	uint64_t	px_gen;
 };
 
 static inline uint32_t __device__ __host__
@@ -611,6 +621,9 @@ void	bk_aux_free(nxsgpu_index_t *ix);
 int	bk_aux_build(nxsgpu_index_t *ix, const nxsgpu_bknode_t *nodes, uint32_t n);
 
 void	sg_free(nxsgpu_index_t *ix);		/* everything nxsgpu_suggest has built (index destroy) */
+
+/* ---- nxs_gpu_prefix.hip ---- */
+void	px_free(nxsgpu_index_t *ix);		/* everything nxsgpu_complete has built (index destroy) */
 
 /* ---- nxs_gpu_plan.hip ---- */
 void	delete_worklist(worklist_t *);

@@ -83,5 +83,20 @@ nxs_sugg_t *	nxs_test_sugg_build(const char *token, size_t token_len, bool dropp
 		    unsigned count, const uint8_t *const *terms, const size_t *lens, const unsigned *dists,
 		    const uint64_t *dfs);
 
+/* prefix completion: the host ranker (nxs_complete.h) over a dictionary handed in (term i has id i + 1), the
+ * parameters as nxs_index_complete and a search read them, a completion object built by hand, a query's
+ * prefix leaves marked, resolved with the host ranker and spliced (-> nxs_query_repr of the result), and the
+ * filter stages a prefix takes */
+void		nxs_test_complete_host(const uint8_t *const *terms, const uint32_t *lens, const uint32_t *dfs,
+		    uint32_t n_terms, const uint8_t *prefix, size_t len, uint32_t k,
+		    uint32_t *out_ids, uint32_t *out_df, uint32_t *count, uint32_t *matches);
+int		nxs_test_complete_params(nxs_t *, nxs_params_t *, unsigned *k, int *prefixmatch, unsigned *prefix_limit);
+nxs_sugg_t *	nxs_test_compl_build(const char *prefix, size_t prefix_len, uint64_t matches, unsigned count,
+		    const uint8_t *const *terms, const size_t *lens, const uint64_t *dfs);
+char *		nxs_test_prefix_query(const char *query, const char *const *words, const uint32_t *dfs,
+		    uint32_t n_words, bool lowercase, bool prefixmatch, uint32_t prefix_limit, uint32_t *n_prefix,
+		    char *prefixes, size_t cap);
+char *		nxs_test_filter_prefix(const char *basedir, int stages, const char *s, int *act);
+
 #endif /* NXS_TEST_HOOKS */
 #endif /* NXS_HOOKS_H */

@@ -223,6 +223,11 @@ nxs_filters_t *nxs_filters_create(const char *basedir, const char *const *names,
 	    const char *lang, const char **err);
 void	nxs_filters_destroy(nxs_filters_t *);
 int	nxs_filters_run(nxs_filters_t *, char **val, size_t *len);
+/* ... on the stages of the pipeline that are in `stages` only (a query prefix: the normalizer alone) */
+#define	NXS_FSTAGE_NORMALIZER	(1u << 1)
+#define	NXS_FSTAGE_STOPWORDS	(1u << 2)
+#define	NXS_FSTAGE_STEMMER	(1u << 3)
+int	nxs_filters_run_stages(nxs_filters_t *, unsigned stages, char **val, size_t *len);
 /* the English Snowball stemmer (Porter2) on a UTF-8 token, in place -> new length (nxs_stem_en.c) */
 size_t	nxs_stem_en(char *w, size_t len);
 
@@ -261,6 +266,22 @@ typedef struct {
 	uint32_t	term_id;	/* 0 = unresolved */
 } qtok_t;
 
+/*
+ * A prefix leaf (`term*` under "prefixmatch"): the normalised prefix, and -- once the batch's prefixes have
+ * been resolved (nxsgpu_complete) -- its expansions: the first min(prefix_limit, matches) eligible terms in
+ * the order df descending, term id ascending.  nxs_query_splice puts them in the leaf's place.
+ */
+#define	NXS_PREFIX_MAX		32	/* "prefix_limit" at most */
+typedef struct {
+	size_t		item;		/* the leaf: index into parse.items */
+	char *		val;		/* malloc'd, NUL-terminated */
+	size_t		len;
+	uint32_t	n;		/* expansions */
+	uint32_t	ids[NXS_PREFIX_MAX];
+	const uint8_t *	tval[NXS_PREFIX_MAX];	/* their bytes (the dictionary's) */
+	uint16_t	tlen[NXS_PREFIX_MAX];
+} qpfx_t;
+
 typedef struct qprep {
 	qparse_t	parse;
 	qtok_t *	tokens;		/* token-list order (query.c:89-95) */
@@ -275,9 +296,19 @@ typedef struct qprep {
 	nxsgpu_wide_query_t wplan;	/* arrays owned by this object */
 	char **		heap_vals;	/* token values a filter grew beyond the arena's reserve */
 	size_t		n_heap_vals;
+	qpfx_t *	pfx;		/* prefix leaves, in the order they were met (right to left) */
+	size_t		n_pfx;
+	bool		has_prefix;	/* some leaf was read as a prefix: the plan depends on prefix_limit and the df */
+	void *		splice;		/* nxs_query_splice: the items, tokens and strings that replaced the arena's */
 } qprep_t;
 
 void	nxs_query_prepare(const nxs_index_t *, const char *query, qprep_t *out);
+/* the same; prefixmatch: a leaf from a free-form string that ends in `*` (and is longer) is a prefix leaf --
+ * kept out of the token list, recorded in out->pfx */
+void	nxs_query_prepare_px(const nxs_index_t *, const char *query, bool prefixmatch, qprep_t *out);
+/* every prefix leaf becomes (e1 OR e2 OR ... OR em), the token list what the rewritten query's would be;
+ * m = 0: the leaf stays the empty set.  0 / -1 (out of memory) */
+int	nxs_query_splice(qprep_t *);
 int	nxs_query_compile(qprep_t *);	/* after term ids are final */
 void	nxs_query_release(qprep_t *);
 void	nxs_query_release_scratch(qprep_t *);	/* parse + token list; keeps errors and plans */

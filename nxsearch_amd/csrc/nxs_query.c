@@ -409,10 +409,79 @@ nxs_query_repr(const qparse_t *q)
 
 /* ---- prepare: token set -------------------------------------------------- */
 
+/*
+ * Is the n-th operand of the query a free-form string?  The parser keeps no trace of it and stays as it
+ * is: the query is scanned once more (prefix mode only).  Operands keep their source order in the postfix
+ * program, so the n-th leaf item is the n-th operand token.  ff[] has room for one flag per leaf.
+ */
+static void
+operand_kinds(const char *query, uint8_t *ff, size_t cap)
+{
+	scanner_t sc = { .cur = query, .line_start = query, .line = 1 };
+	qtoken_t tk;
+	size_t n = 0;
+
+	while ((tk = scan_next(&sc)) != QTK_EOF) {
+		if ((tk == QTK_FF_STRING || tk == QTK_QUOTED_STRING) && n < cap) {
+			ff[n++] = tk == QTK_FF_STRING;
+		}
+	}
+}
+
 void
 nxs_query_prepare(const nxs_index_t *idx, const char *query, qprep_t *out)
 {
+	nxs_query_prepare_px(idx, query, false, out);
+}
+
+/*
+ * A prefix leaf: the star goes, the rest takes the normalizer / lowercase stage only -- a fragment is no
+ * word: no stop words, no stemmer (nxs_filters_run_stages).  1 = recorded in out->pfx, 0 = the prefix
+ * normalised to nothing (the leaf is the empty set), -1 = error (out->errcode set).
+ */
+static int
+prepare_prefix(const nxs_index_t *idx, qprep_t *out, size_t item, const char *str, size_t len)
+{
+	char *val = strndup(str, len);
+	qpfx_t *px;
+
+	if (!val) {
+		out->errcode = NXS_ERR_SYSTEM;
+		out->errmsg = strdup("out of memory");
+		return -1;
+	}
+	if (idx && idx->filters) {
+		if (nxs_filters_run_stages(idx->filters, NXS_FSTAGE_NORMALIZER, &val, &len) < 0) {
+			free(val);
+			out->errcode = NXS_ERR_FATAL;
+			out->errmsg = strdup("query_prepare() failed");
+			return -1;
+		}
+	} else if (idx && idx->lowercase) {
+		for (size_t c = 0; c < len; c++) {
+			if (val[c] >= 'A' && val[c] <= 'Z') {
+				val[c] += 32;
+			}
+		}
+	}
+	if (len == 0) {
+		free(val);
+		return 0;
+	}
+	px = &out->pfx[out->n_pfx++];
+	memset(px, 0, sizeof(*px));
+	px->item = item;
+	px->val = val;
+	px->len = len;
+	return 1;
+}
+
+void
+nxs_query_prepare_px(const nxs_index_t *idx, const char *query, bool prefixmatch, qprep_t *out)
+{
 	qparse_t *pr = &out->parse;
+	uint8_t *ff = NULL;
+	size_t n_leaves = 0, leaf;
 
 	memset(out, 0, sizeof(*out));
 	nxs_query_parse(query, pr);
@@ -432,6 +501,21 @@ nxs_query_prepare(const nxs_index_t *idx, const char *query, qprep_t *out)
 		return;
 	}
 	memset(out->tokens, 0, (pr->n + 1) * sizeof(qtok_t));
+	if (prefixmatch && strchr(query, '*')) {
+		for (size_t k = 0; k < pr->n; k++) {
+			n_leaves += pr->items[k].op == 0;
+		}
+		ff = calloc(n_leaves + 1, 1);
+		out->pfx = calloc(n_leaves + 1, sizeof(qpfx_t));
+		if (!ff || !out->pfx) {
+			free(ff);
+			out->errcode = NXS_ERR_SYSTEM;
+			out->errmsg = strdup("out of memory");
+			return;
+		}
+		operand_kinds(query, ff, n_leaves);
+	}
+	leaf = n_leaves;
 
 	/*
 	 * query_prepare pops its explicit stack from the back after pushing
@@ -449,6 +533,15 @@ nxs_query_prepare(const nxs_index_t *idx, const char *query, qprep_t *out)
 		}
 		len = strlen(it->str);
 		val = it->str;		/* (in the arena; a filter may hand back a malloc'd string) */
+		if (ff && ff[--leaf] && len >= 2 && val[len - 1] == '*') {
+			/* a prefix leaf: no token, never looked up, never fuzzy-matched */
+			out->has_prefix = true;
+			if (prepare_prefix(idx, out, k, val, len - 1) < 0) {
+				free(ff);
+				return;
+			}
+			continue;
+		}
 		/* tokenize_value: the index's filter pipeline on the leaf string
 		 * (tokenizer.c:205-227; nxs_filters.c) */
 		if (idx && idx->filters) {
@@ -480,6 +573,7 @@ nxs_query_prepare(const nxs_index_t *idx, const char *query, qprep_t *out)
 				/* FILT_ERROR => query_prepare fails (search.c:199-203) */
 				out->errcode = NXS_ERR_FATAL;
 				out->errmsg = strdup("query_prepare() failed");
+				free(ff);
 				return;
 			}
 		} else if (idx && idx->lowercase) {
@@ -504,6 +598,109 @@ nxs_query_prepare(const nxs_index_t *idx, const char *query, qprep_t *out)
 		}
 		it->token = (int)j;
 	}
+	free(ff);
+}
+
+/*
+ * The prefix leaves' expansions into the program and the token list: leaf i becomes e1 e2 OR e3 OR ... --
+ * the postfix form of (e1 OR e2 OR ... OR em) -- and the token list is made again the way query_prepare
+ * would make it for the rewritten query: leaves right to left, equal bytes share a token, first seen
+ * first.  An expansion is a resolved term: its token carries the term id, takes no filter and no lookup.
+ * Everything new lives in one block (q->splice) that replaces the arena's arrays.
+ */
+int
+nxs_query_splice(qprep_t *q)
+{
+	qparse_t *pr = &q->parse;
+	const qtok_t *old = q->tokens;
+	size_t n_items = pr->n, n_exp = 0, str_bytes = 0, o = 0, n_tok = 0;
+	qitem_t *items;
+	qtok_t *tokens;
+	uint32_t *exp_id;		/* [item] the term id of an expansion leaf, 0: any other item */
+	char *strs, *blk;
+
+	if (!q->n_pfx || q->splice) {
+		return 0;
+	}
+	for (size_t i = 0; i < q->n_pfx; i++) {
+		const qpfx_t *px = &q->pfx[i];
+
+		n_exp += px->n;
+		n_items += px->n ? 2 * (size_t)px->n - 2 : 0;
+		for (uint32_t e = 0; e < px->n; e++) {
+			str_bytes += (size_t)px->tlen[e] + 1;
+		}
+	}
+	blk = malloc((n_items + 1) * (sizeof(qitem_t) + sizeof(uint32_t)) +
+	    (q->n_tokens + n_exp + 1) * sizeof(qtok_t) + str_bytes + 8);
+	if (!blk) {
+		return -1;
+	}
+	items = (qitem_t *)blk;
+	tokens = (qtok_t *)(items + n_items + 1);
+	exp_id = (uint32_t *)(tokens + q->n_tokens + n_exp + 1);
+	strs = (char *)(exp_id + n_items + 1);
+	/* the program (pfx[] is in right-to-left order: the leaves come up from its end) */
+	for (size_t k = 0, next = q->n_pfx; k < pr->n; k++) {
+		const qpfx_t *px = next && q->pfx[next - 1].item == k ? &q->pfx[--next] : NULL;
+
+		if (!px || !px->n) {
+			exp_id[o] = 0;
+			items[o++] = pr->items[k];	/* (a prefix without expansions: token -1, the empty set) */
+			continue;
+		}
+		for (uint32_t e = 0; e < px->n; e++) {
+			memcpy(strs, px->tval[e], px->tlen[e]);
+			strs[px->tlen[e]] = '\0';
+			items[o].op = 0;
+			items[o].str = strs;
+			items[o].token = -1;
+			exp_id[o++] = px->ids[e];
+			strs += px->tlen[e] + 1;
+			if (e) {
+				items[o].op = NXSGPU_OP_OR;
+				items[o].str = NULL;
+				items[o].token = -1;
+				exp_id[o++] = 0;
+			}
+		}
+	}
+	/* the token list */
+	for (size_t k = o; k-- > 0; ) {
+		qitem_t *it = &items[k];
+		qtok_t t;
+		size_t j;
+
+		if (it->op != 0) {
+			continue;
+		}
+		if (exp_id[k]) {
+			t.value = it->str;
+			t.len = strlen(it->str);
+			t.term_id = exp_id[k];
+		} else if (it->token >= 0) {
+			t = old[it->token];
+		} else {
+			continue;
+		}
+		for (j = 0; j < n_tok; j++) {
+			if (tokens[j].len == t.len && memcmp(tokens[j].value, t.value, t.len) == 0) {
+				break;
+			}
+		}
+		if (j == n_tok) {
+			tokens[n_tok++] = t;
+		} else if (!tokens[j].term_id) {
+			tokens[j].term_id = t.term_id;
+		}
+		it->token = (int)j;
+	}
+	pr->items = items;
+	pr->n = o;
+	q->splice = blk;
+	q->tokens = tokens;
+	q->n_tokens = n_tok;
+	return 0;
 }
 
 /*
@@ -660,6 +857,16 @@ nxs_query_release_scratch(qprep_t *q)
 	free(q->heap_vals);
 	q->heap_vals = NULL;
 	q->n_heap_vals = 0;
+	if (q->pfx) {
+		for (size_t j = 0; j < q->n_pfx; j++) {
+			free(q->pfx[j].val);
+		}
+		free(q->pfx);
+		free(q->splice);	/* (the spliced items and tokens) */
+		q->pfx = NULL;
+		q->n_pfx = 0;
+		q->splice = NULL;
+	}
 	q->tokens = NULL;
 	q->n_tokens = 0;
 	nxs_query_free(&q->parse);
