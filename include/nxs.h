@@ -47,7 +47,7 @@ typedef enum {
 nxs_err_t	nxs_get_error(const nxs_t *, const char **);	/* nxs.h:48 */
 
 /* Parameters (nxs.h:54-67); the query path reads limit / algo / fuzzymatch / total / prefixmatch /
- * prefix_limit, nxs_index_suggest reads suggest_limit / suggest_maxdist, nxs_index_complete complete_limit */
+ * prefix_limit / explain, nxs_index_suggest reads suggest_limit / suggest_maxdist, nxs_index_complete complete_limit */
 struct nxs_params;
 typedef struct nxs_params nxs_params_t;
 
@@ -102,6 +102,37 @@ void		nxs_resp_release(nxs_resp_t *);
  * nxs_index_plan_batch() ignores the key.
  */
 bool		nxs_resp_total(const nxs_resp_t *, uint64_t *total);
+
+/*
+ * Explanations (new; the reference has no such key).  A search whose params carry "explain": true (bool,
+ * default false; with it false or absent nothing changes) also reports, for every returned doc, what each
+ * token of the query's token list added to its score.  The token list is what the query RESOLVED to -- after
+ * the filters, the fuzzy lookup and the expansion of prefix leaves; right to left, merged, unresolved tokens
+ * left out, a term reached twice listed twice -- in the order the scores are added (run_query_logic,
+ * search.c:236-270).  Every token whose term holds the doc contributes, also one that stands under a NOT or in
+ * another OR branch: the expression only decides which docs are returned.  The contributions of the present
+ * tokens, added in f32 in ascending token order starting from 0, ARE the returned score, bit for bit.
+ *
+ * nxs_resp_tokens():  m, the length of the token list; 0 if the search did not ask or matched nothing.
+ * nxs_resp_token():   the bytes of the dictionary term token j resolved to (owned by the response,
+ *                     NUL-terminated); false if j is out of range.
+ * nxs_resp_explain(): result i (iteration order), token j: the term count of the doc and the float the token
+ *                     added; false = absent (the doc does not hold the term), out of range, or not asked.
+ *                     The out pointers may be NULL.
+ * The JSON of an asking search: {"results":[{"doc_id":N,"score":X,"terms":[{"t":J,"tf":N,"score":X},...]},
+ * ...],"count":K[,"total":M],"tokens":["term",...]} -- "terms" holds the present tokens in ascending J.
+ *
+ * The explanation belongs to the snapshot the results came from (a batch finished early because the files
+ * moved is explained before the index follows them) and covers every limit and plan size.  Served by
+ * nxs_index_search, nxs_index_search_batch[_begin/_end] (any mix of asking and non-asking batches in flight;
+ * query-sharded: every rank explains the responses it holds from its own replica, no collective) and
+ * nxs_docshard_search_batch (each row comes from the shard that holds the doc).  REFUSED -- -1 and
+ * NXS_ERR_INVALID "explain is not available on a ranked doc-shard batch" -- by
+ * nxs_docshard_search_batch_rank().  nxs_index_plan_batch() ignores the key.
+ */
+unsigned	nxs_resp_tokens(const nxs_resp_t *);
+bool		nxs_resp_token(const nxs_resp_t *, unsigned j, const char **term, size_t *len);
+bool		nxs_resp_explain(const nxs_resp_t *, unsigned i, unsigned j, float *score, uint32_t *tf);
 
 /*
  * Spelling suggestions (new; the reference has no "did you mean" call).  For one raw token -- not a

@@ -352,6 +352,40 @@ int		nxsgpu_complete(nxsgpu_index_t *, const uint8_t *bytes, const uint32_t *off
 void		nxsgpu_complete_profile(nxsgpu_index_t *, double out[NXSGPU_COMPLETE_PROF], int reset);
 
 /*
+ * ---- explanations -------------------------------------------------------------------
+ *
+ * nxsgpu_explain: for final results, what every token of the query's token list added to every returned doc.
+ * run_query_logic (search.c:236-270) adds rank(term, doc) to a doc's score for every token, in list order,
+ * whose term holds the doc (the expression only decides which docs are looked at; a term listed twice adds
+ * twice), so the present cells of a row, added in f32 in ascending token order, are the doc's score bit for
+ * bit.
+ *
+ * rows: for query q the results doc_ids[res_off[q] .. res_off[q+1]) x its n_tok[q] tokens
+ * (term ids tok_ids[tok_off[q] ..]); out_tf / out_imp are [sum_q results(q) * n_tok(q)], row-major
+ * (result, token); tf == 0 means absent (a posting's tf is >= 1); found[r] == 0: doc id r is not a
+ * live doc of THIS index (doc shards) and its row is all absent.  (out_* and found are indexed from the
+ * first result of the call, res_off[0].)  A term id outside the dictionary and a term without live
+ * postings are absent everywhere.  0 / -1.
+ *
+ * The pass (k_explain: a lane per result, the token loop wave-uniform, nxs_explain.h's searches) reads the
+ * index's arrays as they are at call time, on a stream and a grow-only workspace of its own: allowed while
+ * batches and fuzzy passes are in flight, takes none of their slots; blocking.  It is cut into chunks of at
+ * most NXS_GPU_EXPLAIN_ROWS cells (default 2 M: 36 MB of workspace at most).  An index that is never asked
+ * allocates, uploads and launches nothing.  The ranking function's impacts must be materialised (they are
+ * for any result that exists).
+ *
+ * nxsgpu_explain_profile: since the last reset -- out[0] passes (calls that reached the device), out[1]
+ * HIP-event ms of k_explain (with nxsgpu_set_profiling only), out[2] cells, out[3] cells present, out[4]
+ * chunks (kernel launches).
+ */
+#define	NXSGPU_EXPLAIN_PROF	8
+int		nxsgpu_explain(nxsgpu_index_t *, int algo, uint32_t n_queries,
+		    const uint32_t *tok_off, const uint32_t *tok_ids,
+		    const uint64_t *res_off, const uint64_t *doc_ids,
+		    uint32_t *out_tf, float *out_imp, uint8_t *found);
+void		nxsgpu_explain_profile(nxsgpu_index_t *, double out[NXSGPU_EXPLAIN_PROF], int reset);
+
+/*
  * ---- host batches as fixed-size records; query sharding over several GPUs ----
  *
  * The reference scales out by running independent worker processes

@@ -92,13 +92,16 @@ NXS_H_SYMBOLS = [
     "nxs_index_suggest", "nxs_index_suggest_batch", "nxs_sugg_count", "nxs_sugg_matches", "nxs_sugg_dropped",
     "nxs_sugg_get", "nxs_sugg_tojson", "nxs_sugg_release",
     "nxs_index_complete", "nxs_index_complete_batch",
+    "nxs_resp_tokens", "nxs_resp_token", "nxs_resp_explain",
 ]
 # csrc/nxs_hooks.h: test hooks + bench accessors, only in builds with -DNXS_TEST_HOOKS (the default)
 NXS_HOOK_SYMBOLS = ["nxs_index_device", "nxs_index_host_profile", "nxs_index_shard_info", "nxs_test_pool", "nxs_test_assemble",
                     "nxs_test_fixup_scan", "nxs_test_inject_failure", "nxs_test_count_tile_widths",
                     "nxs_test_suggest_host", "nxs_test_suggest_params", "nxs_test_sugg_build",
                     "nxs_test_complete_host", "nxs_test_complete_params", "nxs_test_compl_build",
-                    "nxs_test_prefix_query", "nxs_test_filter_prefix"]
+                    "nxs_test_prefix_query", "nxs_test_filter_prefix",
+                    "nxs_test_explain_params", "nxs_test_resp_build", "nxs_test_explain_search",
+                    "nxs_test_explain_ordinal"]
 NXS_GPU_H_SYMBOLS = [
     "nxsgpu_device_count", "nxsgpu_last_error", "nxsgpu_index_create",
     "nxsgpu_index_destroy", "nxsgpu_index_df", "nxsgpu_index_postings",
@@ -118,6 +121,7 @@ NXS_GPU_H_SYMBOLS = [
     "nxsgpu_batch_end_totals", "nxsgpu_count_tile_widths", "nxsgpu_count_profile",
     "nxsgpu_suggest", "nxsgpu_suggest_profile",
     "nxsgpu_complete", "nxsgpu_complete_profile",
+    "nxsgpu_explain", "nxsgpu_explain_profile",
 ]
 
 _lib = None
@@ -189,6 +193,12 @@ def lib():
     L.nxs_resp_release.argtypes = [vp]
     L.nxs_resp_total.restype = C.c_bool
     L.nxs_resp_total.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.nxs_resp_tokens.restype = C.c_uint
+    L.nxs_resp_tokens.argtypes = [vp]
+    L.nxs_resp_token.restype = C.c_bool
+    L.nxs_resp_token.argtypes = [vp, C.c_uint, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.nxs_resp_explain.restype = C.c_bool
+    L.nxs_resp_explain.argtypes = [vp, C.c_uint, C.c_uint, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]
     L.nxs_index_suggest.restype = vp
     L.nxs_index_suggest.argtypes = [vp, vp, cp, C.c_size_t]
     L.nxs_index_suggest_batch.restype = C.c_int
@@ -258,6 +268,8 @@ def lib():
                                   C.POINTER(C.c_uint32)]
     L.nxsgpu_complete_profile.restype = None
     L.nxsgpu_complete_profile.argtypes = [vp, C.POINTER(C.c_double), C.c_int]
+    L.nxsgpu_explain_profile.restype = None
+    L.nxsgpu_explain_profile.argtypes = [vp, C.POINTER(C.c_double), C.c_int]
     # host-only test hooks
     L.nxs_test_query_repr.restype = vp
     L.nxs_test_query_repr.argtypes = [cp, C.POINTER(vp)]
@@ -339,10 +351,11 @@ class Nxs:
         return Index(self, h)
 
     def docshard_search_batch(self, shards, queries, limit=None, algo=None, fuzzymatch=None, total=False,
-                              prefixmatch=None):
+                              prefixmatch=None, explain=False):
         """nxs_docshard_search_batch(): one batch over all shards, merged exactly.
         total: every result list also carries `.total` (the sum of the shards' counts).
-        (prefixmatch: a batch with a prefix leaf is refused -- NXS_ERR_INVALID.)"""
+        (prefixmatch: a batch with a prefix leaf is refused -- NXS_ERR_INVALID.)
+        explain: every list carries `.tokens` and `.explain` (each row from the shard that holds the doc)."""
         L = lib()
         L.nxs_docshard_search_batch.restype = C.c_int
         L.nxs_docshard_search_batch.argtypes = [C.POINTER(C.c_void_p), C.c_uint, C.c_void_p,
@@ -353,7 +366,7 @@ class Nxs:
         qs = (C.c_char_p * max(n, 1))(*[_b(q) for q in queries])
         resps = (C.c_void_p * max(n, 1))()
         errs = (C.c_int * max(n, 1))()
-        p = _make_params(limit, algo, fuzzymatch, total, prefixmatch)
+        p = _make_params(limit, algo, fuzzymatch, total, prefixmatch, explain=explain)
         try:
             r = L.nxs_docshard_search_batch(hs, len(shards), p, qs, n, resps, errs)
         finally:
@@ -364,7 +377,7 @@ class Nxs:
         out = []
         for i in range(n):
             if resps[i]:
-                out.append(_drain(resps[i]))
+                out.append(_drain(resps[i], explain))
                 L.nxs_resp_release(resps[i])
             else:
                 out.append(NxsError(errs[i], "query %d failed" % i))
@@ -383,16 +396,17 @@ class Nxs:
                 out.append(NxsError(errs[i], "query %d failed" % i))
         return out
 
-    def docshard_search_batch_rank(self, shard, queries, limit=None, algo=None, fuzzymatch=None, total=False):
+    def docshard_search_batch_rank(self, shard, queries, limit=None, algo=None, fuzzymatch=None, total=False,
+                                   explain=False):
         """nxs_docshard_search_batch_rank(): this rank's shard + one all-gather + merge.
-        (total: refused for now -- NXS_ERR_INVALID.)"""
+        (total, explain: refused -- NXS_ERR_INVALID.)"""
         L = lib()
         L.nxs_docshard_search_batch_rank.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_char_p), C.c_size_t,
                                                      C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
         n = len(queries)
         qs = (C.c_char_p * max(n, 1))(*[_b(q) for q in queries])
         resps, errs = (C.c_void_p * max(n, 1))(), (C.c_int * max(n, 1))()
-        p = _make_params(limit, algo, fuzzymatch, total)
+        p = _make_params(limit, algo, fuzzymatch, total, explain=explain)
         try:
             r = L.nxs_docshard_search_batch_rank(shard._h, p, qs, n, resps, errs)
         finally:
@@ -524,8 +538,13 @@ class Nxs:
 
 class Results(list):
     """The result list of a search that asked for the total match count: a list like any
-    other, with `.total` = how many docs matched (nxs_resp_total)."""
+    other, with `.total` = how many docs matched (nxs_resp_total).  Of a search that asked for explanations:
+    `.tokens` = the dictionary terms the query's token list resolved to ([bytes, ...], nxs_resp_token) and
+    `.explain` = per result the present tokens [(j, tf, score), ...] in ascending j (nxs_resp_explain); both
+    empty if nothing matched."""
     total = None
+    tokens = None
+    explain = None
 
 
 class Suggestions(list):
@@ -569,9 +588,10 @@ def _suggest_params(limit=None, maxdist=None):
     return p
 
 
-def _make_params(limit=None, algo=None, fuzzymatch=None, total=False, prefixmatch=None, prefix_limit=None):
+def _make_params(limit=None, algo=None, fuzzymatch=None, total=False, prefixmatch=None, prefix_limit=None,
+                 explain=False):
     if limit is None and algo is None and fuzzymatch is None and not total and prefixmatch is None \
-            and prefix_limit is None:
+            and prefix_limit is None and not explain:
         return None
     L = lib()
     p = L.nxs_params_create()
@@ -587,10 +607,12 @@ def _make_params(limit=None, algo=None, fuzzymatch=None, total=False, prefixmatc
         L.nxs_params_set_bool(p, b"prefixmatch", bool(prefixmatch))
     if prefix_limit is not None:
         L.nxs_params_set_uint(p, b"prefix_limit", prefix_limit)
+    if explain:
+        L.nxs_params_set_bool(p, b"explain", True)
     return p
 
 
-def _drain(resp):
+def _drain(resp, explain=False):
     L = lib()
     out = []
     d, s = C.c_uint64(), C.c_float()
@@ -602,6 +624,22 @@ def _drain(resp):
     if L.nxs_resp_total(resp, C.byref(t)):
         out = Results(out)
         out.total = t.value
+    m = L.nxs_resp_tokens(resp)
+    if explain or m:
+        if not isinstance(out, Results):
+            out = Results(out)
+        term, ln, sc, tf = C.c_void_p(), C.c_size_t(), C.c_float(), C.c_uint32()
+        out.tokens = []
+        for j in range(m):
+            assert L.nxs_resp_token(resp, j, C.byref(term), C.byref(ln))
+            out.tokens.append(C.string_at(term.value, ln.value))
+        out.explain = []
+        for i in range(len(out)):
+            row = []
+            for j in range(m):
+                if L.nxs_resp_explain(resp, i, j, C.byref(sc), C.byref(tf)):
+                    row.append((j, tf.value, sc.value))
+            out.explain.append(row)
     return out
 
 
@@ -617,12 +655,13 @@ class Index:
         return lib().nxs_index_device(self._h)
 
     def search(self, query, limit=None, algo=None, fuzzymatch=None, json=False, params_json=None, total=False,
-               prefixmatch=None, prefix_limit=None):
+               prefixmatch=None, prefix_limit=None, explain=False):
         """nxs_index_search(): -> [(doc_id, score), ...] (or the JSON text).
         params_json: the parameters as the Lua binding passes them (nxs_params_fromjson).
         total: also count the matches -- the list then carries `.total` (the JSON a "total" member).
         prefixmatch: a free-form leaf `term*` stands for the OR of its `prefix_limit` (1..32, default 8) best
-        completions."""
+        completions.
+        explain: the list also carries `.tokens` and `.explain` (class Results; the JSON "terms" / "tokens")."""
         L = lib()
         if params_json is not None:
             pj = _b(params_json)
@@ -630,7 +669,7 @@ class Index:
             if not p:
                 self.nxs._raise()
         else:
-            p = _make_params(limit, algo, fuzzymatch, total, prefixmatch, prefix_limit)
+            p = _make_params(limit, algo, fuzzymatch, total, prefixmatch, prefix_limit, explain)
         q = _b(query)
         try:
             resp = L.nxs_index_search(self._h, p, q, len(q))
@@ -643,20 +682,21 @@ class Index:
             if json:
                 n = C.c_size_t()
                 return _take(L.nxs_resp_tojson(resp, C.byref(n)))
-            return _drain(resp)
+            return _drain(resp, explain)
         finally:
             L.nxs_resp_release(resp)
 
     def search_batch(self, queries, limit=None, algo=None, fuzzymatch=None, total=False,
-                     prefixmatch=None, prefix_limit=None):
+                     prefixmatch=None, prefix_limit=None, explain=False):
         """nxs_index_search_batch(): list of result lists; a failed query
-        yields an NxsError instance in its slot.  total: every list carries `.total`."""
+        yields an NxsError instance in its slot.  total: every list carries `.total`; explain: `.tokens` and
+        `.explain`."""
         L = lib()
         n = len(queries)
         qs = (C.c_char_p * n)(*[_b(q) for q in queries])
         resps = (C.c_void_p * n)()
         errs = (C.c_int * n)()
-        p = _make_params(limit, algo, fuzzymatch, total, prefixmatch, prefix_limit)
+        p = _make_params(limit, algo, fuzzymatch, total, prefixmatch, prefix_limit, explain)
         try:
             r = L.nxs_index_search_batch(self._h, p, qs, n, resps, errs)
         finally:
@@ -667,20 +707,21 @@ class Index:
         out = []
         for i in range(n):
             if resps[i]:
-                out.append(_drain(resps[i]))
+                out.append(_drain(resps[i], explain))
                 L.nxs_resp_release(resps[i])
             else:
                 out.append(NxsError(errs[i], "query %d failed" % i))
         return out
 
     def search_batch_begin(self, queries, limit=None, algo=None, fuzzymatch=None, total=False,
-                           prefixmatch=None, prefix_limit=None):
+                           prefixmatch=None, prefix_limit=None, explain=False):
         """nxs_index_search_batch_begin(): queue a batch (at most NXS_BATCHES_INFLIGHT = 4 in flight).
-        total: the lists search_batch_end() returns for this batch carry `.total`."""
+        total: the lists search_batch_end() returns for this batch carry `.total`; explain: `.tokens` and
+        `.explain`."""
         L = lib()
         n = len(queries)
         qs = (C.c_char_p * max(n, 1))(*[_b(q) for q in queries])
-        p = _make_params(limit, algo, fuzzymatch, total, prefixmatch, prefix_limit)
+        p = _make_params(limit, algo, fuzzymatch, total, prefixmatch, prefix_limit, explain)
         try:
             r = L.nxs_index_search_batch_begin(self._h, p, qs, n)
         finally:
@@ -689,6 +730,7 @@ class Index:
         if r != 0:
             self.nxs._raise()
         self._pending = getattr(self, "_pending", []) + [n]
+        self._pending_explain = getattr(self, "_pending_explain", []) + [bool(explain)]
 
     def search_batch_end(self):
         """nxs_index_search_batch_end(): the oldest batch's result lists."""
@@ -701,10 +743,15 @@ class Index:
         if r < 0:
             self.nxs._raise()
         self._pending = pend[1:]
+        pex = getattr(self, "_pending_explain", [])
+        if len(pex) != len(pend):       # (a caller edited _pending: the flag only matters for empty results)
+            pex = [False] * len(pend)
+        explain = pex[0] if pex else False
+        self._pending_explain = pex[1:]
         out = []
         for i in range(n):
             if resps[i]:
-                out.append(_drain(resps[i]))
+                out.append(_drain(resps[i], explain))
                 L.nxs_resp_release(resps[i])
             else:
                 out.append(NxsError(errs[i], "query %d failed" % i))
@@ -878,6 +925,14 @@ class Index:
         lib().nxsgpu_complete_profile(self.device, out, 1 if reset else 0)
         return {"passes": int(out[0]), "ms": out[1], "range_ms": out[2], "select_ms": out[3], "build_ms": out[4],
                 "entries": int(out[5]), "host_prefixes": int(out[6]), "builds": int(out[7])}
+
+    def explain_profile(self, reset=False):
+        """nxsgpu_explain_profile(): explain passes, HIP-event ms of k_explain (profiling on), (result, token)
+        cells, cells present, chunks (kernel launches)."""
+        out = (C.c_double * 8)()
+        lib().nxsgpu_explain_profile(self.device, out, 1 if reset else 0)
+        return {"passes": int(out[0]), "ms": out[1], "cells": int(out[2]), "present": int(out[3]),
+                "chunks": int(out[4])}
 
     def set_plan_cache(self, on=True):
         """bench: the index's plan cache (query string -> compiled plan) on / off."""

@@ -29,6 +29,7 @@
 #include "nxs_hooks.h"
 #include "nxs_suggest.h"
 #include "nxs_complete.h"
+#include "nxs_explain.h"
 
 struct plan_cache;
 static void plan_cache_destroy(struct plan_cache *);
@@ -1191,6 +1192,7 @@ nxs_index_set_plan_cache(nxs_index_t *idx, int on)
  */
 struct resp_slab {
 	size_t		refs;
+	void *		ex;		/* the batch's explanations (explain_attach), or NULL: one block, freed with the slab */
 };
 
 struct nxs_resp {
@@ -1201,6 +1203,13 @@ struct nxs_resp {
 	struct resp_slab *slab;		/* NULL: ids/scores are this response's own */
 	bool		has_total;	/* the search asked for the total match count */
 	uint64_t	total;
+	/* "explain" (all in the slab's explain block; n_tok == 0: not asked, or nothing matched) */
+	unsigned	n_tok;		/* tokens of the query's token list */
+	const char *const *tok;		/* [n_tok] the dictionary terms they resolved to, NUL-terminated */
+	const uint32_t *tok_len;	/* [n_tok] */
+	const uint32_t *ex_tf;		/* [count][n_tok] term count of (result, token), 0 = absent */
+	const float *	ex_imp;		/* [count][n_tok] what the token added to the result's score */
+	bool		explained;	/* the search asked (the JSON then carries "tokens", be it empty) */
 };
 
 typedef struct {
@@ -1223,6 +1232,7 @@ slab_begin(slab_builder_t *b, size_t n, size_t total)
 	}
 	b->slab = (struct resp_slab *)m;
 	b->slab->refs = 0;
+	b->slab->ex = NULL;
 	b->resps = (nxs_resp_t *)(m + hdr);
 	b->ids = (nxs_doc_id_t *)(m + hdr + rs);
 	b->scores = (float *)(b->ids + total);
@@ -1243,9 +1253,22 @@ slab_resp(slab_builder_t *b, size_t i, unsigned count)
 	r->slab = b->slab;
 	r->has_total = false;
 	r->total = 0;
+	r->n_tok = 0;
+	r->tok = NULL;
+	r->tok_len = NULL;
+	r->ex_tf = NULL;
+	r->ex_imp = NULL;
+	r->explained = false;
 	b->used += count;
 	b->slab->refs++;
 	return r;
+}
+
+static void
+slab_free(struct resp_slab *s)
+{
+	free(s->ex);
+	free(s);
 }
 
 void
@@ -1253,7 +1276,7 @@ nxs_resp_release(nxs_resp_t *r)
 {
 	if (r->slab) {
 		if (--r->slab->refs == 0) {
-			free(r->slab);
+			slab_free(r->slab);
 		}
 		return;
 	}
@@ -1357,15 +1380,69 @@ fmt_real(char *out, double v)
 	return o;
 }
 
-/* {"results":[{"doc_id":N,"score":X},...],"count":K}  (results.c:80-82,153-161,218) */
+unsigned
+nxs_resp_tokens(const nxs_resp_t *r)
+{
+	return r->n_tok;
+}
+
+bool
+nxs_resp_token(const nxs_resp_t *r, unsigned j, const char **term, size_t *len)
+{
+	if (j >= r->n_tok) {
+		return false;
+	}
+	if (term) {
+		*term = r->tok[j];
+	}
+	if (len) {
+		*len = r->tok_len[j];
+	}
+	return true;
+}
+
+bool
+nxs_resp_explain(const nxs_resp_t *r, unsigned i, unsigned j, float *score, uint32_t *tf)
+{
+	size_t at;
+
+	if (i >= r->count || j >= r->n_tok) {
+		return false;
+	}
+	at = (size_t)i * r->n_tok + j;
+	if (r->ex_tf[at] == 0) {
+		return false;
+	}
+	if (score) {
+		*score = r->ex_imp[at];
+	}
+	if (tf) {
+		*tf = r->ex_tf[at];
+	}
+	return true;
+}
+
+static size_t json_str(char *out, const char *s, size_t n);
+
+/*
+ * {"results":[{"doc_id":N,"score":X},...],"count":K}  (results.c:80-82,153-161,218); with "total" it ends
+ * ...,"total":M}; an explained response (new) carries per result "terms":[{"t":J,"tf":N,"score":X},...] -- the
+ * present tokens in ascending J -- and ends ...,"tokens":["term",...]}
+ */
 char *
 nxs_resp_tojson(nxs_resp_t *r, size_t *len)
 {
-	const size_t cap = 80 + (size_t)r->count * 88;
-	char *s = malloc(cap);
+	size_t cap = 80 + (size_t)r->count * 88;
+	char *s;
 	size_t o = 0;
 
-	if (!s) {
+	if (r->explained) {
+		cap += 16 + (size_t)r->count * (16 + (size_t)r->n_tok * 72);
+		for (unsigned j = 0; j < r->n_tok; j++) {
+			cap += 4 + 6 * (size_t)r->tok_len[j];
+		}
+	}
+	if ((s = malloc(cap)) == NULL) {
 		return NULL;
 	}
 	o += sprintf(s + o, "{\"results\":[");
@@ -1373,13 +1450,42 @@ nxs_resp_tojson(nxs_resp_t *r, size_t *len)
 		o += sprintf(s + o, "%s{\"doc_id\":%llu,\"score\":", i ? "," : "",
 		    (unsigned long long)r->ids[i]);
 		o += fmt_real(s + o, (double)r->scores[i]);
+		if (r->explained) {
+			const char *sep = "";
+
+			o += sprintf(s + o, ",\"terms\":[");
+			for (unsigned j = 0; j < r->n_tok; j++) {
+				const size_t at = (size_t)i * r->n_tok + j;
+
+				if (r->ex_tf[at] == 0) {
+					continue;
+				}
+				o += sprintf(s + o, "%s{\"t\":%u,\"tf\":%u,\"score\":", sep, j, r->ex_tf[at]);
+				o += fmt_real(s + o, (double)r->ex_imp[at]);
+				s[o++] = '}';
+				sep = ",";
+			}
+			s[o++] = ']';
+		}
 		s[o++] = '}';
 	}
 	if (r->has_total) {
-		o += sprintf(s + o, "],\"count\":%u,\"total\":%llu}", r->count, (unsigned long long)r->total);
+		o += sprintf(s + o, "],\"count\":%u,\"total\":%llu", r->count, (unsigned long long)r->total);
 	} else {
-		o += sprintf(s + o, "],\"count\":%u}", r->count);
+		o += sprintf(s + o, "],\"count\":%u", r->count);
 	}
+	if (r->explained) {
+		o += sprintf(s + o, ",\"tokens\":[");
+		for (unsigned j = 0; j < r->n_tok; j++) {
+			if (j) {
+				s[o++] = ',';
+			}
+			o += json_str(s + o, r->tok[j], r->tok_len[j]);
+		}
+		s[o++] = ']';
+	}
+	s[o++] = '}';
+	s[o] = '\0';
 	if (len) {
 		*len = o;
 	}
@@ -1395,6 +1501,7 @@ typedef struct {
 	bool		total;		/* "total": also count the matches (nxs_resp_total) */
 	bool		prefixmatch;	/* "prefixmatch": a free-form leaf `term*` stands for its best completions */
 	unsigned	prefix_limit;	/* "prefix_limit": how many of them (1..NXS_PREFIX_MAX, default 8) */
+	bool		explain;	/* "explain": per result and token the term count and the score contribution */
 } search_params_t;
 
 /* get_search_params: search.c:78-112 */
@@ -1410,6 +1517,7 @@ get_search_params(nxs_index_t *idx, nxs_params_t *params, search_params_t *sp)
 	sp->total = false;
 	sp->prefixmatch = false;
 	sp->prefix_limit = 8;
+	sp->explain = false;
 	sp->algo = idx->algo;
 	if (!params) {
 		return 0;
@@ -1433,6 +1541,9 @@ get_search_params(nxs_index_t *idx, nxs_params_t *params, search_params_t *sp)
 	if (nxs_params_get_bool(params, "prefixmatch", &fl) == 0 && fl) {
 		sp->prefixmatch = true;
 	}
+	if (nxs_params_get_bool(params, "explain", &fl) == 0 && fl) {
+		sp->explain = true;
+	}
 	if (nxs_params_get_uint(params, "prefix_limit", &v) == 0) {
 		if (v < 1 || v > NXS_PREFIX_MAX) {
 			nxs_decl_err(idx->nxs, NXS_ERR_INVALID, "invalid prefix_limit (1..%d)", NXS_PREFIX_MAX);
@@ -1441,6 +1552,180 @@ get_search_params(nxs_index_t *idx, nxs_params_t *params, search_params_t *sp)
 		sp->prefix_limit = (unsigned)v;
 	}
 	return 0;
+}
+
+/* ---- explanations ("explain") --------------------------------------------------------- */
+
+/* one response to explain: its query's token list as the device saw it (nxsgpu_query_t::term_id) */
+typedef struct {
+	nxs_resp_t *	r;
+	uint32_t	n_tok;
+	const uint32_t *term_ids;
+} ex_item_t;
+
+/*
+ * Explanations of a batch's responses: ONE nxsgpu_explain call per device index for all of them, on the
+ * final results (after exact re-queries) and before the device index can move.  `shards`: the index, or the
+ * doc shards of a collection -- they hold disjoint docs, so every result's row comes from the one shard
+ * whose `found` is set (none, or two: NXS_ERR_FATAL).  The dictionary is shards[0]'s (the same on every
+ * shard); term bytes are copied by term id, so a plan from the plan cache explains like a parsed one.
+ * Everything lands in one block that the responses' slab owns.  Responses with no result keep n_tok == 0.
+ * 0, or -1 with the error declared (the responses are untouched then).
+ */
+static int
+explain_attach(nxs_index_t *const *shards, unsigned n_shards, int algo, const ex_item_t *items, size_t n_items,
+    struct resp_slab *slab)
+{
+	const nxs_index_t *dict = shards[0];
+	nxs_t *nxs = dict->nxs;
+	uint32_t *tok_off = NULL, *tok_ids = NULL, *s_tf = NULL;
+	uint64_t *res_off = NULL, *doc_ids = NULL;
+	float *s_imp = NULL;
+	uint8_t *found = NULL, *seen = NULL, *blk = NULL;
+	size_t n_tok = 0, n_res = 0, cells = 0, bytes = 0, nq = 0, o;
+	int ret = -1;
+
+	for (size_t i = 0; i < n_items; i++) {
+		const ex_item_t *it = &items[i];
+
+		if (!it->r->count || !it->n_tok) {
+			continue;
+		}
+		for (uint32_t j = 0; j < it->n_tok; j++) {
+			if (it->term_ids[j] < 1 || it->term_ids[j] > dict->last_id) {
+				nxs_decl_err(nxs, NXS_ERR_FATAL, "explain: a plan names term %u, which the dictionary lacks",
+				    it->term_ids[j]);
+				return -1;
+			}
+			bytes += (size_t)dict->terms[it->term_ids[j]].len + 1;
+		}
+		nq++;
+		n_tok += it->n_tok;
+		n_res += it->r->count;
+		cells += (size_t)it->r->count * it->n_tok;
+	}
+	if (nq == 0) {
+		return 0;
+	}
+	if (nq > UINT32_MAX - 1 || n_tok > UINT32_MAX / 2) {
+		nxs_decl_err(nxs, NXS_ERR_LIMIT, "explain: batch too large");
+		return -1;
+	}
+	tok_off = malloc((nq + 1) * sizeof(uint32_t));
+	tok_ids = malloc(n_tok * sizeof(uint32_t));
+	res_off = malloc((nq + 1) * sizeof(uint64_t));
+	doc_ids = malloc(n_res * sizeof(uint64_t));
+	found = malloc(n_res);
+	/* block: term pointers | tf | contributions | term lengths | term bytes */
+	const size_t o_tf = n_tok * sizeof(char *), o_imp = o_tf + cells * 4, o_len = o_imp + cells * 4,
+	    o_bytes = o_len + n_tok * 4;
+	blk = malloc(o_bytes + bytes + 1);
+	if (n_shards > 1) {
+		s_tf = malloc(cells * sizeof(uint32_t));
+		s_imp = malloc(cells * sizeof(float));
+		seen = calloc(n_res, 1);
+	}
+	if (!tok_off || !tok_ids || !res_off || !doc_ids || !found || !blk ||
+	    (n_shards > 1 && (!s_tf || !s_imp || !seen))) {
+		nxs_decl_err(nxs, NXS_ERR_SYSTEM, "out of memory");
+		goto out;
+	}
+	const char **b_tok = (const char **)blk;
+	uint32_t *b_tf = (uint32_t *)(blk + o_tf), *b_len = (uint32_t *)(blk + o_len);
+	float *b_imp = (float *)(blk + o_imp);
+	char *b_bytes = (char *)(blk + o_bytes);
+
+	tok_off[0] = 0;
+	res_off[0] = 0;
+	o = 0;
+	for (size_t i = 0, q = 0; i < n_items; i++) {
+		const ex_item_t *it = &items[i];
+
+		if (!it->r->count || !it->n_tok) {
+			continue;
+		}
+		for (uint32_t j = 0; j < it->n_tok; j++) {
+			const hterm_t *t = &dict->terms[it->term_ids[j]];
+			const size_t at = tok_off[q] + j;
+
+			tok_ids[at] = it->term_ids[j];
+			b_tok[at] = b_bytes + o;
+			b_len[at] = t->len;
+			memcpy(b_bytes + o, t->val, t->len);
+			b_bytes[o + t->len] = '\0';
+			o += (size_t)t->len + 1;
+		}
+		memcpy(doc_ids + res_off[q], it->r->ids, (size_t)it->r->count * sizeof(uint64_t));
+		tok_off[q + 1] = tok_off[q] + it->n_tok;
+		res_off[q + 1] = res_off[q] + it->r->count;
+		q++;
+	}
+	if (n_shards == 1) {
+		if (nxsgpu_explain(shards[0]->dev, algo, (uint32_t)nq, tok_off, tok_ids, res_off, doc_ids, b_tf, b_imp, found) != 0) {
+			nxs_decl_err(nxs, NXS_ERR_FATAL, "device explain failed: %s", nxsgpu_last_error());
+			goto out;
+		}
+		for (size_t r = 0; r < n_res; r++) {
+			if (!found[r]) {
+				nxs_decl_err(nxs, NXS_ERR_FATAL, "explain: doc %llu was returned but is not in the index",
+				    (unsigned long long)doc_ids[r]);
+				goto out;
+			}
+		}
+	} else {
+		for (unsigned s = 0; s < n_shards; s++) {
+			if (nxsgpu_explain(shards[s]->dev, algo, (uint32_t)nq, tok_off, tok_ids, res_off, doc_ids, s_tf, s_imp, found) != 0) {
+				nxs_decl_err(nxs, NXS_ERR_FATAL, "device explain failed on shard %u: %s", s, nxsgpu_last_error());
+				goto out;
+			}
+			for (size_t q = 0, c = 0; q < nq; q++) {
+				const size_t nt = tok_off[q + 1] - tok_off[q];
+
+				for (uint64_t r = res_off[q]; r < res_off[q + 1]; r++, c += nt) {
+					if (!found[r]) {
+						continue;
+					}
+					if (seen[r]) {
+						nxs_decl_err(nxs, NXS_ERR_FATAL, "explain: doc %llu is held by two shards",
+						    (unsigned long long)doc_ids[r]);
+						goto out;
+					}
+					seen[r] = 1;
+					memcpy(b_tf + c, s_tf + c, nt * 4);
+					memcpy(b_imp + c, s_imp + c, nt * 4);
+				}
+			}
+		}
+		for (size_t r = 0; r < n_res; r++) {
+			if (!seen[r]) {
+				nxs_decl_err(nxs, NXS_ERR_FATAL, "explain: doc %llu was returned but no shard holds it",
+				    (unsigned long long)doc_ids[r]);
+				goto out;
+			}
+		}
+	}
+	for (size_t i = 0, q = 0, c = 0; i < n_items; i++) {
+		const ex_item_t *it = &items[i];
+		nxs_resp_t *r = it->r;
+
+		if (!r->count || !it->n_tok) {
+			continue;
+		}
+		r->n_tok = it->n_tok;
+		r->tok = b_tok + tok_off[q];
+		r->tok_len = b_len + tok_off[q];
+		r->ex_tf = b_tf + c;
+		r->ex_imp = b_imp + c;
+		c += (size_t)r->count * it->n_tok;
+		q++;
+	}
+	slab->ex = blk;
+	blk = NULL;
+	ret = 0;
+out:
+	free(tok_off); free(tok_ids); free(res_off); free(doc_ids); free(found);
+	free(s_tf); free(s_imp); free(seen); free(blk);
+	return ret;
 }
 
 /*
@@ -2158,6 +2443,10 @@ pend_release(nxs_pend_t *p)
 		nxs_query_release(&p->prep[i]);
 	}
 	free(p->prep);
+	for (size_t i = 0; p->xprep && i < p->n; i++) {
+		nxs_query_release(&p->xprep[i]);	/* (this rank's slice: never filled) */
+	}
+	free(p->xprep);
 	late_free(p->late);
 	for (size_t i = 0; p->st_resps && i < p->n; i++) {
 		if (p->st_resps[i]) {		/* stashed and never collected */
@@ -2491,6 +2780,7 @@ nxs_index_search_batch_begin(nxs_index_t *idx, nxs_params_t *params,
 	pd->limit = sp.limit;
 	pd->algo = sp.algo;
 	pd->want_total = sp.total;
+	pd->want_explain = sp.explain;
 	pd->world = 1;
 	/* query sharding: fixed-size records, limit <= NXSGPU_BIG_K;
 	 * larger limits run replicated -- every rank computes the whole batch */
@@ -2619,6 +2909,25 @@ nxs_index_search_batch_begin(nxs_index_t *idx, nxs_params_t *params,
 	t1 = now_s();
 	plan_back(idx, &sp, queries + lo, nl, pd->prep, &fz);
 	idx->hp_back += now_s() - t1;
+	if (sp.explain && pd->world > 1 && !idx->shard_local) {
+		/*
+		 * This rank will hold every response of the batch and explains them all from its replica, with no
+		 * collective: it needs the token lists of the other ranks' queries too.  Every replica has the same
+		 * dictionary, so planning them here yields what their owners planned.  (Sharded batches never leave
+		 * a fuzzy pass running: plan_batch's blocking pass is the only one.)
+		 */
+		pd->xprep = calloc(n ? n : 1, sizeof(qprep_t));
+		if (!pd->xprep) {
+			nxs_decl_err(nxs, NXS_ERR_SYSTEM, "out of memory");
+		}
+		if (!pd->xprep || (lo && plan_batch(idx, &sp, queries, lo, pd->xprep) == -1) ||
+		    (hi < n && plan_batch(idx, &sp, queries + hi, n - hi, pd->xprep + hi) == -1)) {
+			if (collective) {
+				goto abort_collective;
+			}
+			goto out;
+		}
+	}
 	t1 = now_s();
 	idx->hp_plan += t1 - t0;
 	if (sp.limit <= NXSGPU_BIG_K) {
@@ -2928,6 +3237,57 @@ fixup_verify(const uint8_t *blocks, uint32_t W, uint32_t n_slots, uint32_t k, si
 	return ar;
 }
 
+/* the token list the device saw for a planned query (NULL plan: nothing to explain) */
+static inline void
+ex_item_of(ex_item_t *it, nxs_resp_t *r, const qprep_t *q)
+{
+	it->r = r;
+	it->n_tok = q->wide ? q->wplan.n_tokens : q->plan.n_tokens;
+	it->term_ids = q->wide ? q->wplan.term_id : q->plan.term_id;
+}
+
+/*
+ * "explain": every response of the batch that this rank holds gets its explanation, from this rank's device
+ * index, in one pass.  Called where the responses are materialised (batch_end_core -- also for a batch that
+ * a later _begin finishes early because the files moved: the explanation belongs to the snapshot the results
+ * came from, and the device index has not moved yet).  The slice [lo, hi) has its plans in pd->prep, the
+ * other ranks' queries (all blocks gathered, own-slice mode off) in pd->xprep.
+ */
+static int
+explain_batch(nxs_index_t *idx, const nxs_pend_t *pd, nxs_resp_t **resps, struct resp_slab *slab)
+{
+	nxs_index_t *one[1] = { idx };
+	ex_item_t *items = malloc((pd->n ? pd->n : 1) * sizeof(ex_item_t));
+	size_t ni = 0;
+	int ret;
+
+	if (!items) {
+		nxs_decl_err(idx->nxs, NXS_ERR_SYSTEM, "out of memory");
+		return -1;
+	}
+	for (size_t i = 0; i < pd->n; i++) {
+		const bool mine = i >= pd->lo && i < pd->hi;
+		const qprep_t *q = mine ? &pd->prep[i - pd->lo] : pd->xprep ? &pd->xprep[i] : NULL;
+
+		if (!resps[i]) {
+			continue;
+		}
+		resps[i]->explained = true;
+		if (!q || q->errcode || q->empty || !resps[i]->count) {
+			if (!q && resps[i]->count) {
+				nxs_decl_err(idx->nxs, NXS_ERR_FATAL, "explain: no plan for query %zu", i);
+				free(items);
+				return -1;
+			}
+			continue;
+		}
+		ex_item_of(&items[ni++], resps[i], q);
+	}
+	ret = explain_attach(one, 1, pd->algo, items, ni, slab);
+	free(items);
+	return ret;
+}
+
 static int
 batch_end_core(nxs_index_t *idx, nxs_pend_t *pd, nxs_resp_t **resps, nxs_err_t *errs)
 {
@@ -3131,6 +3491,31 @@ batch_end_core(nxs_index_t *idx, nxs_pend_t *pd, nxs_resp_t **resps, nxs_err_t *
 			}
 			memcpy(idx->emu_block, blocks, v.block_bytes);
 			idx->emu_block_len = v.block_bytes;
+			if (pd->want_explain) {
+				/*
+				 * An emulated rank holds its own block alone: what it can materialise -- and explain,
+				 * as a real rank does from its replica -- is its own slice (the other slices' responses
+				 * stay NULL, as in own-slice mode).
+				 */
+				uint8_t *wb = calloc((size_t)W * v.block_bytes + 1, 1);
+				int rc;
+
+				if (!wb) {
+					nxs_decl_err(nxs, NXS_ERR_SYSTEM, "out of memory");
+					goto out;
+				}
+				memcpy(wb + (size_t)pd->rank * v.block_bytes, blocks, v.block_bytes);
+				rc = resps_from_blocks(nxs, pd, n, W, v.n_slots, v.k, wb, resps, errs, &sb, &failed, pd->rank);
+				free(wb);
+				if (rc == -1 || (sb.slab && sb.slab->refs && explain_batch(idx, pd, resps, sb.slab) != 0)) {
+					goto out;
+				}
+				if (sb.slab && sb.slab->refs == 0) {
+					slab_free(sb.slab);
+				}
+				ret = failed;
+				goto out;
+			}
 			ret = 0;
 			goto out;
 		}
@@ -3197,8 +3582,12 @@ batch_end_core(nxs_index_t *idx, nxs_pend_t *pd, nxs_resp_t **resps, nxs_err_t *
 			resps[pd->lo + i]->total = tot[i];	/* (a query that resolves to nothing: 0) */
 		}
 	}
+	/* (after the exact re-queries have replaced inexact records, before the device index can move) */
+	if (pd->want_explain && sb.slab && sb.slab->refs && explain_batch(idx, pd, resps, sb.slab) != 0) {
+		goto out;
+	}
 	if (sb.slab && sb.slab->refs == 0) {
-		free(sb.slab);		/* every query failed */
+		slab_free(sb.slab);		/* every query failed */
 	}
 	ret = failed;
 out:
@@ -3208,7 +3597,7 @@ out:
 		for (size_t i = 0; i < n; i++) {
 			resps[i] = NULL;
 		}
-		free(sb.slab);
+		slab_free(sb.slab);
 	}
 	if (res.counts) {
 		nxsgpu_results_free(&res);
@@ -3875,6 +4264,130 @@ nxs_index_complete(nxs_index_t *idx, nxs_params_t *params, const char *prefix, s
 }
 
 #ifdef NXS_TEST_HOOKS
+/* explanations: the "explain" key as a search reads it (0, or -1 with the error declared) */
+int
+nxs_test_explain_params(nxs_t *nxs, nxs_params_t *params, int *explain)
+{
+	nxs_index_t fake = { .nxs = nxs };
+	search_params_t sp;
+
+	nxs_clear_error(nxs);
+	if (get_search_params(&fake, params, &sp) == -1) {
+		return -1;
+	}
+	*explain = sp.explain;
+	return 0;
+}
+
+/*
+ * A response built by hand (accessors and JSON without an index): `count` results; explained: n_tok tokens
+ * (terms / lens) and the cells tf / imp [count][n_tok], tf == 0 = absent.  NULL: out of memory.
+ */
+nxs_resp_t *
+nxs_test_resp_build(unsigned count, const uint64_t *ids, const float *scores, bool has_total, uint64_t total,
+    bool explained, unsigned n_tok, const uint8_t *const *terms, const size_t *lens, const uint32_t *tf,
+    const float *imp)
+{
+	slab_builder_t sb = { 0 };
+	nxs_resp_t *r;
+	size_t bytes = 0, o = 0;
+	const size_t cells = (size_t)count * n_tok;
+
+	if (slab_begin(&sb, 1, count) == -1) {
+		return NULL;
+	}
+	r = slab_resp(&sb, 0, count);
+	memcpy(r->ids, ids, (size_t)count * sizeof(uint64_t));
+	memcpy(r->scores, scores, (size_t)count * sizeof(float));
+	r->has_total = has_total;
+	r->total = total;
+	r->explained = explained;
+	if (explained && n_tok) {
+		for (unsigned j = 0; j < n_tok; j++) {
+			bytes += lens[j] + 1;
+		}
+		const size_t o_tf = n_tok * sizeof(char *), o_imp = o_tf + cells * 4, o_len = o_imp + cells * 4,
+		    o_bytes = o_len + (size_t)n_tok * 4;
+		uint8_t *blk = malloc(o_bytes + bytes + 1);
+
+		if (!blk) {
+			nxs_resp_release(r);
+			return NULL;
+		}
+		const char **b_tok = (const char **)blk;
+		uint32_t *b_len = (uint32_t *)(blk + o_len);
+		char *b_bytes = (char *)(blk + o_bytes);
+
+		memcpy(blk + o_tf, tf, cells * 4);
+		memcpy(blk + o_imp, imp, cells * 4);
+		for (unsigned j = 0; j < n_tok; j++) {
+			b_tok[j] = b_bytes + o;
+			b_len[j] = (uint32_t)lens[j];
+			memcpy(b_bytes + o, terms[j], lens[j]);
+			b_bytes[o + lens[j]] = '\0';
+			o += lens[j] + 1;
+		}
+		r->n_tok = n_tok;
+		r->tok = b_tok;
+		r->tok_len = b_len;
+		r->ex_tf = (const uint32_t *)(blk + o_tf);
+		r->ex_imp = (const float *)(blk + o_imp);
+		sb.slab->ex = blk;
+	}
+	return r;
+}
+
+/*
+ * The searches of nxs_explain.h on a list handed in (dt[0 .. n): doc << 32 | tf, ascending docs below n_docs):
+ * for every docs[i], pos[i] = nxs_ex_find's answer (UINT64_MAX: absent) and lower[i] = nxs_ex_lower over the
+ * whole list.  bitmap: through a block-presence bitmap and rank directory built here as the device index
+ * builds its rows (k_blkmap_fill).  0 / -1 (out of memory).
+ */
+int
+nxs_test_explain_search(const uint64_t *dt, uint64_t n, bool bitmap, uint32_t n_docs, const uint32_t *docs, size_t nd,
+    uint64_t *pos, uint64_t *lower)
+{
+	const uint64_t words = ((uint64_t)n_docs + 4095) / 4096;
+	uint64_t *bm = NULL;
+	uint32_t *rk = NULL;
+
+	if (bitmap) {
+		bm = calloc(words ? words : 1, sizeof(uint64_t));
+		rk = calloc(words + 1, sizeof(uint32_t));
+		if (!bm || !rk) {
+			free(bm);
+			free(rk);
+			return -1;
+		}
+		for (uint64_t w = 0, i = 0; w <= words; w++) {
+			while (i < n && ((dt[i] >> 32) >> 12) < w) {
+				i++;
+			}
+			rk[w] = (uint32_t)i;
+		}
+		for (uint64_t i = 0; i < n; i++) {
+			const uint32_t d = (uint32_t)(dt[i] >> 32);
+			bm[d >> 12] |= UINT64_C(1) << ((d >> 6) & 63);
+		}
+	}
+	for (size_t i = 0; i < nd; i++) {
+		pos[i] = docs[i] < n_docs ? nxs_ex_find(dt, 0, n, bm, rk, docs[i]) : nxs_ex_find(dt, 0, n, NULL, NULL, docs[i]);
+		lower[i] = nxs_ex_lower(dt, 0, n, docs[i]);
+	}
+	free(bm);
+	free(rk);
+	return 0;
+}
+
+/* nxs_ex_ordinal for every q[i] over ids[0 .. n) (UINT64_MAX: not a live doc) */
+void
+nxs_test_explain_ordinal(const uint64_t *ids, uint64_t n, const uint64_t *q, size_t nq, uint64_t *out)
+{
+	for (size_t i = 0; i < nq; i++) {
+		out[i] = nxs_ex_ordinal(ids, n, q[i]);
+	}
+}
+
 /* the host ranker of completions (nxs_complete.h) over a dictionary handed in: term i has id i + 1 */
 void
 nxs_test_complete_host(const uint8_t *const *terms, const uint32_t *lens, const uint32_t *dfs, uint32_t n_terms,
@@ -4168,6 +4681,12 @@ docshard_search(nxs_index_t *const *local, unsigned n_local, unsigned n_shards, 
 		nxs_decl_err(nxs, NXS_ERR_INVALID, "total is not available on a sharded batch");
 		return -1;
 	}
+	/* (the rank form: a rank holds one shard, so the rows of the other shards' docs would have to travel in a
+	 * collective of their own; every rank passes the same params, so every rank refuses) */
+	if (sp.explain && (rank_form || ranks || gathered || my_block)) {
+		nxs_decl_err(nxs, NXS_ERR_INVALID, "explain is not available on a ranked doc-shard batch");
+		return -1;
+	}
 	for (unsigned s = 0; s < n_local; s++) {
 		/* (rank form: every rank carries the mark, so none enters the collective) */
 		if (local[s]->ds_inconsistent) {
@@ -4386,8 +4905,38 @@ docshard_search(nxs_index_t *const *local, unsigned n_local, unsigned n_shards, 
 			}
 		}
 	}
+	/* "explain": every shard is asked about the merged results; a row comes from the shard that holds the doc */
+	if (sp.explain && sb.slab->refs) {
+		ex_item_t *items = malloc(n * sizeof(ex_item_t));
+		size_t ni = 0;
+		int rc;
+
+		if (!items) {
+			nxs_decl_err(nxs, NXS_ERR_SYSTEM, "out of memory");
+			rc = -1;
+		} else {
+			for (size_t i = 0; i < n; i++) {
+				if (resps[i]) {
+					resps[i]->explained = true;
+					if (!prep[i].empty && resps[i]->count) {
+						ex_item_of(&items[ni++], resps[i], &prep[i]);
+					}
+				}
+			}
+			rc = explain_attach(local, n_local, sp.algo, items, ni, sb.slab);
+			free(items);
+		}
+		if (rc != 0) {
+			for (size_t i = 0; i < n; i++) {
+				resps[i] = NULL;
+			}
+			slab_free(sb.slab);
+			sb.slab = NULL;
+			goto out;
+		}
+	}
 	if (sb.slab && sb.slab->refs == 0) {
-		free(sb.slab);
+		slab_free(sb.slab);
 	}
 	ret = failed;
 out:
@@ -5296,7 +5845,7 @@ nxs_test_assemble(const uint8_t *blocks, uint32_t world, uint32_t n_slots, uint3
 		return -1;
 	}
 	if (sb.slab && sb.slab->refs == 0) {
-		free(sb.slab);
+		slab_free(sb.slab);
 	}
 	free(fake.errmsg);
 	return failed;

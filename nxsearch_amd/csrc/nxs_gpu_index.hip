@@ -130,6 +130,7 @@ cfg_from_env(gpu_cfg_t &c)
 		const char *e = getenv("NXS_GPU_COMPLETE");
 		c.complete_host = e && !strcmp(e, "host");
 	}
+	c.explain_rows = u64("NXS_GPU_EXPLAIN_ROWS", 2ull << 20, 1, 1ull << 26);
 }
 
 /* ------------------------------------------------------------------ */
@@ -658,6 +659,7 @@ nxsgpu_index_destroy(nxsgpu_index_t *ix)
 	(void)hipFree(ix->d_bk_bytes);
 	sg_free(ix);
 	px_free(ix);
+	ex_free(ix);
 	bk_aux_free(ix);
 	(void)hipFree(ix->ws);
 	(void)hipFree(ix->fz);

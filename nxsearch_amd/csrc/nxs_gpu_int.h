@@ -30,6 +30,8 @@
  *                         suggestions over the same screen (k_sg_dist, k_sg_select)
  *  nxs_gpu_prefix.hip     prefix completion: the live terms in byte order (k_px_keys + radix sort), a
  *                         range per prefix (k_px_range), its k best by df (k_px_select)
+ *  nxs_gpu_explain.hip    k_explain: per returned doc and query token the term count and the float the
+ *                         token added to the score, looked up in the CSR (nxs_explain.h)
  *  nxs_gpu_plan.hip       host only: query classes, the work list (build_worklist) and
  *                         the layout of a batch's arrays (batch_layout)
  *  nxs_gpu_search.hip     kernel dispatch, blocking search, batches in flight
@@ -178,6 +180,8 @@ struct gpu_cfg_t {
 	uint32_t	count_mode;	/* NXS_GPU_COUNT=auto|tile|req|scan (COUNT_*): which kernel counts a query's matches */
 	bool		suggest_host;	/* NXS_GPU_SUGGEST=host: every suggestion from the host ranker (nxs_suggest.h): the cross-check */
 	bool		complete_host;	/* NXS_GPU_COMPLETE=host: every completion from the host ranker (nxs_complete.h): the cross-check */
+	uint64_t	explain_rows;	/* NXS_GPU_EXPLAIN_ROWS (2 M): (result, token) cells per explain pass -- 17 bytes of workspace a
+					 * cell at most (one-token queries), 36 MB */
 };
 enum : uint32_t { COUNT_AUTO = 0, COUNT_TILE = 1, COUNT_REQ = 2, COUNT_SCAN = 3 };
 
@@ -396,6 +400,8 @@ struct nxsgpu_index {
 	 */
 	struct px_state_t *px;
 	uint64_t	px_gen;
+	/* explanations (nxsgpu_explain, nxs_gpu_explain.hip): stream, workspace, staging; nothing until the first call */
+	struct ex_state_t *ex;
 };
 
 static inline uint32_t __device__ __host__
@@ -624,6 +630,9 @@ void	sg_free(nxsgpu_index_t *ix);		/* everything nxsgpu_suggest has built (index
 
 /* ---- nxs_gpu_prefix.hip ---- */
 void	px_free(nxsgpu_index_t *ix);		/* everything nxsgpu_complete has built (index destroy) */
+
+/* ---- nxs_gpu_explain.hip ---- */
+void	ex_free(nxsgpu_index_t *ix);		/* everything nxsgpu_explain has built (index destroy) */
 
 /* ---- nxs_gpu_plan.hip ---- */
 void	delete_worklist(worklist_t *);

@@ -98,5 +98,17 @@ char *		nxs_test_prefix_query(const char *query, const char *const *words, const
 		    char *prefixes, size_t cap);
 char *		nxs_test_filter_prefix(const char *basedir, int stages, const char *s, int *act);
 
+/* explanations: the "explain" key as a search reads it, a response built by hand from given arrays (accessors
+ * and the JSON writer without an index; cells [count][n_tok], tf == 0 = absent), and the searches of the shared
+ * header nxs_explain.h over a list handed in (pos: nxs_ex_find, UINT64_MAX = absent; lower: nxs_ex_lower;
+ * bitmap: through a block bitmap + rank directory built from the list) */
+int		nxs_test_explain_params(nxs_t *, nxs_params_t *, int *explain);
+nxs_resp_t *	nxs_test_resp_build(unsigned count, const uint64_t *ids, const float *scores, bool has_total,
+		    uint64_t total, bool explained, unsigned n_tok, const uint8_t *const *terms, const size_t *lens,
+		    const uint32_t *tf, const float *imp);
+int		nxs_test_explain_search(const uint64_t *dt, uint64_t n, bool bitmap, uint32_t n_docs,
+		    const uint32_t *docs, size_t nd, uint64_t *pos, uint64_t *lower);
+void		nxs_test_explain_ordinal(const uint64_t *ids, uint64_t n, const uint64_t *q, size_t nq, uint64_t *out);
+
 #endif /* NXS_TEST_HOOKS */
 #endif /* NXS_HOOKS_H */

@@ -83,6 +83,9 @@ typedef struct nxs_pend {
 	bool		active;
 	bool		on_device;	/* queued through nxsgpu_batch_begin */
 	bool		want_total;	/* params "total": count every query's matches */
+	bool		want_explain;	/* params "explain": per-token contributions of every result (explain_batch) */
+	struct qprep *	xprep;		/* [n] or NULL: "explain" on a query-sharded batch whose every response this rank
+					 * materialises -- the plans of the OTHER ranks' slices (this rank's are prep) */
 	size_t		n;		/* queries of the whole batch */
 	size_t		lo, hi;		/* this rank's slice */
 	uint32_t	cap;		/* record slots per rank */
