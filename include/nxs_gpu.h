@@ -282,7 +282,7 @@ int		nxsgpu_fuzzy(nxsgpu_index_t *, const uint8_t *tok_bytes,
  * The same search split in two (no visit counts): _begin queues the device pass on the fuzzy stream and
  * returns a slot (>= 0; -1 error; -2 all NXSGPU_FZ_SLOTS slots taken), _end -- with the slot and the same
  * tokens -- waits and delivers.  The host's planning of the NEXT batch and the scans of the batches in
- * flight run meanwhile (nxs_api.c: a batch with misses is finished by the next
+ * flight run meanwhile (nxs_batch.c: a batch with misses is finished by the next
  * nxs_index_search_batch_begin).  Passes run, and are to be ended, in the order they were begun;
  * nxsgpu_fuzzy() refuses to run while one is in flight.
  */
@@ -529,7 +529,7 @@ int		nxsgpu_batches_in_flight(const nxsgpu_index_t *);
  * The caller's worker threads for the host side of a batch (per-query plan -> device form:
  * embarrassingly parallel, 0.15 ms on one thread for 1024 five-term queries): `run` executes
  * body(arg, lo, hi) over [0, n) in chunks on whatever threads it has and returns when all of it
- * is done.  NULL: one thread.  nxs_api.c hands over the nxs_t's pool (the one that parses).
+ * is done.  NULL: one thread.  nxs_pool.c hands over the nxs_t's pool (the one that parses).
  */
 typedef void (*nxsgpu_body_t)(void *arg, size_t lo, size_t hi);
 typedef void (*nxsgpu_parallel_t)(void *ctx, nxsgpu_body_t body, void *arg, size_t n, size_t chunk);

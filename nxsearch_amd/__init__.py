@@ -865,25 +865,29 @@ class Index:
             return list(ids[:n]), list(vis[:n])
         return list(ids[:n])
 
+    def _lookup_batch(self, call, strings, p, noun, json):
+        """One nxs_index_suggest_batch / _complete_batch call: `strings` in, params `p` (released here, may be
+        None) -> a list of Suggestions, one per string (an NxsError instance in the slot of one that failed)."""
+        n = len(strings)
+        out = (C.c_void_p * max(n, 1))()
+        errs = (C.c_int * max(n, 1))()
+        try:
+            ss = (C.c_char_p * max(n, 1))(*[_b(t) for t in strings])
+            r = call(self._h, p, ss, n, out, errs)
+        finally:
+            if p:
+                lib().nxs_params_release(p)
+        if r < 0:
+            self.nxs._raise()
+        return [_drain_sugg(out[i], json) if out[i] else NxsError(errs[i], "%s %d failed" % (noun, i))
+                for i in range(n)]
+
     def suggest(self, tokens, limit=None, maxdist=None, json=False):
         """nxs_index_suggest_batch(): for every raw token (not a query; it goes through the index's filters)
         the dictionary terms within `maxdist` (1 or 2, default 2) that some live doc holds, best `limit`
         (1..32, default 5) by distance, then df descending, then term id -> a list of Suggestions, one per
         token (an NxsError instance in the slot of a token that failed); json: their JSON texts."""
-        L = lib()
-        n = len(tokens)
-        ts = (C.c_char_p * max(n, 1))(*[_b(t) for t in tokens])
-        out = (C.c_void_p * max(n, 1))()
-        errs = (C.c_int * max(n, 1))()
-        p = _suggest_params(limit, maxdist)
-        try:
-            r = L.nxs_index_suggest_batch(self._h, p, ts, n, out, errs)
-        finally:
-            if p:
-                L.nxs_params_release(p)
-        if r < 0:
-            self.nxs._raise()
-        return [_drain_sugg(out[i], json) if out[i] else NxsError(errs[i], "token %d failed" % i) for i in range(n)]
+        return self._lookup_batch(lib().nxs_index_suggest_batch, tokens, _suggest_params(limit, maxdist), "token", json)
 
     def suggest_profile(self, reset=False):
         """nxsgpu_suggest_profile(): HIP-event times of the suggest pass per kernel (profiling on), its queue
@@ -900,23 +904,11 @@ class Index:
         by df descending, then term id -> a list of Suggestions, one per prefix, entries (term, distance =
         len(term) - len(prefix), df), `.matches` exact (an NxsError instance in the slot of a prefix that
         failed: an empty one); json: their JSON texts."""
-        L = lib()
-        n = len(prefixes)
-        ps = (C.c_char_p * max(n, 1))(*[_b(t) for t in prefixes])
-        out = (C.c_void_p * max(n, 1))()
-        errs = (C.c_int * max(n, 1))()
         p = None
         if limit is not None:
-            p = L.nxs_params_create()
-            L.nxs_params_set_uint(p, b"complete_limit", limit)
-        try:
-            r = L.nxs_index_complete_batch(self._h, p, ps, n, out, errs)
-        finally:
-            if p:
-                L.nxs_params_release(p)
-        if r < 0:
-            self.nxs._raise()
-        return [_drain_sugg(out[i], json) if out[i] else NxsError(errs[i], "prefix %d failed" % i) for i in range(n)]
+            p = lib().nxs_params_create()
+            lib().nxs_params_set_uint(p, b"complete_limit", limit)
+        return self._lookup_batch(lib().nxs_index_complete_batch, prefixes, p, "prefix", json)
 
     def complete_profile(self, reset=False):
         """nxsgpu_complete_profile(): HIP-event times of the completion pass per kernel (profiling on), the

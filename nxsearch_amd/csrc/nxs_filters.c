@@ -290,51 +290,23 @@ out:
 	return ret;
 }
 
-/*
- * filter_pipeline_run on one token (tokenizer.c:215).  *val is a malloc'd,
- * NUL-terminated string and may be replaced.  1 = keep (FILT_MUTATION),
- * 0 = discarded (FILT_DISCARD), -1 = FILT_ERROR.
- */
-int
-nxs_filters_run(nxs_filters_t *f, char **val, size_t *len)
+static void
+ascii_lower(char *val, size_t len)
 {
-	for (unsigned s = 0; f && s < f->n_stages; s++) {
-		if (f->stage[s] == F_NORMALIZER) {
-			bool ascii = true;
-
-			for (size_t i = 0; i < *len; i++) {
-				if ((unsigned char)(*val)[i] >= 0x80) {
-					ascii = false;
-					break;
-				}
-			}
-			if (ascii) {
-				for (size_t i = 0; i < *len; i++) {
-					if ((*val)[i] >= 'A' && (*val)[i] <= 'Z') {
-						(*val)[i] += 32;
-					}
-				}
-			} else if (normalize_icu(f, val, len) == -1) {
-				return -1;
-			}
-		} else if (f->stage[s] == F_STOPWORDS) {
-			if (sw_has(f, *val, *len)) {
-				return 0;
-			}
-		} else if (f->stage[s] == F_STEMMER) {
-			/* stemmer_filter: filters_builtin.c:219-238 (in place: never longer) */
-			*len = nxs_stem_en(*val, *len);
-			(*val)[*len] = '\0';
+	for (size_t i = 0; i < len; i++) {
+		if (val[i] >= 'A' && val[i] <= 'Z') {
+			val[i] += 32;
 		}
 	}
-	return 1;
 }
 
 /*
- * The same on a chosen subset of the pipeline's stages (NXS_FSTAGE_* bits): the stages of the index's list
- * that are in `stages` run, in list order, the others are skipped.  A query PREFIX (nxs_index_complete, a
- * `term*` leaf) is a fragment, not a word: it takes the normalizer only -- `th*` must not vanish as a stop
- * word, and a stem of a fragment is not a prefix of the stems.
+ * filter_pipeline_run on one token (tokenizer.c:215), on a chosen subset of the pipeline's stages
+ * (NXS_FSTAGE_* bits): the stages of the index's list that are in `stages` run, in list order, the others
+ * are skipped.  *val is a malloc'd, NUL-terminated string and may be replaced.  1 = keep (FILT_MUTATION),
+ * 0 = discarded (FILT_DISCARD), -1 = FILT_ERROR.  A query PREFIX (nxs_index_complete, a `term*` leaf) is a
+ * fragment, not a word: it takes the normalizer only -- `th*` must not vanish as a stop word, and a stem of
+ * a fragment is not a prefix of the stems.
  */
 int
 nxs_filters_run_stages(nxs_filters_t *f, unsigned stages, char **val, size_t *len)
@@ -353,11 +325,7 @@ nxs_filters_run_stages(nxs_filters_t *f, unsigned stages, char **val, size_t *le
 				}
 			}
 			if (ascii) {
-				for (size_t i = 0; i < *len; i++) {
-					if ((*val)[i] >= 'A' && (*val)[i] <= 'Z') {
-						(*val)[i] += 32;
-					}
-				}
+				ascii_lower(*val, *len);
 			} else if (normalize_icu(f, val, len) == -1) {
 				return -1;
 			}
@@ -366,9 +334,33 @@ nxs_filters_run_stages(nxs_filters_t *f, unsigned stages, char **val, size_t *le
 				return 0;
 			}
 		} else if (f->stage[s] == F_STEMMER) {
+			/* stemmer_filter: filters_builtin.c:219-238 (in place: never longer) */
 			*len = nxs_stem_en(*val, *len);
 			(*val)[*len] = '\0';
 		}
+	}
+	return 1;
+}
+
+/* every stage */
+int
+nxs_filters_run(nxs_filters_t *f, char **val, size_t *len)
+{
+	return nxs_filters_run_stages(f, ~0u, val, len);
+}
+
+/*
+ * What the index does to a query string on `stages`: its pipeline, or -- an index opened with `lowercase`
+ * and no pipeline object (host-only tests) -- the ASCII lowercase of the normalizer.  As nxs_filters_run_stages.
+ */
+int
+nxs_index_filter(const nxs_index_t *idx, unsigned stages, char **val, size_t *len)
+{
+	if (idx->filters) {
+		return nxs_filters_run_stages(idx->filters, stages, val, len);
+	}
+	if (idx->lowercase) {
+		ascii_lower(*val, *len);
 	}
 	return 1;
 }

@@ -3,7 +3,8 @@
  * accessors.  They exist only in builds with -DNXS_TEST_HOOKS (the Makefile's default,
  * which is what tests/ and bench.py load; `make HOOKS=` builds the library without them:
  * the drop-in a consumer of include/nxs.h links).  Python reaches them through ctypes
- * (nxsearch_amd/__init__.py, nxsearch_amd/multi.py).
+ * (nxsearch_amd/__init__.py, nxsearch_amd/multi.py).  A hook that reaches a static function is defined in
+ * that function's unit, beside what it tests; the ones that reach none are in nxs_hooks.c.
  */
 #ifndef NXS_HOOKS_H
 #define NXS_HOOKS_H

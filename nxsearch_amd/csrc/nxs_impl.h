@@ -1,11 +1,14 @@
 /*
- * nxs_impl.h -- private declarations of the C11 host side.
+ * nxs_impl.h -- private declarations of the C11 host side: what nxs_index.c,
+ * nxs_query.c and nxs_filters.c share with the units of the public API (those
+ * have nxs_api_int.h among themselves).
  *
  * Host responsibilities (everything that is not per-posting or per-BK-node
  * work): mapping and validating the two index files, the term dictionary,
  * building and flattening the BK-tree image, query lexing/parsing, token
  * resolution, compiling a query into the device plan, and the nxs_resp_t
- * object.  All per-posting and per-node work happens in nxs_gpu.hip.
+ * object.  All per-posting and per-node work happens on the device, in the
+ * nxs_gpu_*.hip units (nxs_gpu_int.h maps them).
  */
 #ifndef NXS_IMPL_H
 #define NXS_IMPL_H
@@ -98,7 +101,7 @@ typedef struct nxs_pend {
 	 * The batch's misses are being resolved on the device (nxsgpu_fuzzy_begin) and _begin has returned:
 	 * the rest of its front half -- winners into the token lists, compile, queueing on the device -- is
 	 * done by the next _begin (after ITS parse) or by this batch's _end, whichever comes first
-	 * (nxs_api.c: late_finish).  NULL otherwise.
+	 * (nxs_batch.c: late_finish).  NULL otherwise.
 	 */
 	struct late_half *late;
 	/*
@@ -141,7 +144,7 @@ struct nxs_index {
 	/* tests: the n-th next _begin / exact fix-up of this index fails (0: off) */
 	unsigned	test_fail_begin, test_fail_fixup, test_fail_fixup_recv, test_fail_late;
 	bool		resync_pending;	/* sharded: a rank's block flags said its files moved */
-	struct plan_cache *pcache;	/* query string -> compiled plan (nxs_api.c: plan_batch) */
+	struct plan_cache *pcache;	/* query string -> compiled plan (nxs_plan.c: plan_batch) */
 	uint64_t	pend_seq;
 	/* host-side phase times of the batches, seconds (nxs_index_host_profile) */
 	double		hp_plan, hp_queue, hp_wait, hp_resps, hp_begin, hp_end, hp_fzwait, hp_front, hp_fzlaunch, hp_back;
@@ -190,7 +193,7 @@ int	nxs_index_refresh(nxs_index_t *);
 bool	nxs_index_changed(const nxs_index_t *);
 int	nxs_index_bk_sync(nxs_index_t *);
 void	nxs_index_refresh_stats(const nxs_index_t *, uint64_t out[2]);
-/* doc-shard refresh (N4): the pieces of nxs_index_refresh, driven per collection by nxs_api.c */
+/* doc-shard refresh (N4): the pieces of nxs_index_refresh, driven per collection by nxs_docshard.c */
 void	nxs_index_snapshot(const nxs_index_t *, nxs_snap_t *);
 int	nxs_shard_walk(nxs_index_t *, const nxs_snap_t *, uint64_t max_id, bool take_new, nxs_delta_t **);
 int	nxs_shard_merge(nxs_index_t *, nxs_delta_t *);
@@ -231,6 +234,10 @@ int	nxs_filters_run(nxs_filters_t *, char **val, size_t *len);
 #define	NXS_FSTAGE_STOPWORDS	(1u << 2)
 #define	NXS_FSTAGE_STEMMER	(1u << 3)
 int	nxs_filters_run_stages(nxs_filters_t *, unsigned stages, char **val, size_t *len);
+/* the index's pipeline on `stages`, or the ASCII lowercase when the index has `lowercase` only
+ * (hidden: the library's export table is the headers' declarations, not this one) */
+int	nxs_index_filter(const nxs_index_t *, unsigned stages, char **val, size_t *len)
+	    __attribute__((visibility("hidden")));
 /* the English Snowball stemmer (Porter2) on a UTF-8 token, in place -> new length (nxs_stem_en.c) */
 size_t	nxs_stem_en(char *w, size_t len);
 

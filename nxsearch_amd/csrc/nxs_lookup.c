@@ -1,0 +1,545 @@
+/*
+ * nxs_lookup.c -- dictionary lookups by string: spelling suggestions
+ * (nxs_index_suggest) and prefix completions (nxs_index_complete), and the
+ * object both return (nxs_sugg_t).
+ */
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "nxs_api_int.h"
+#include "nxs_hooks.h"
+#include "nxs_suggest.h"
+
+/* ---- the object of both calls (nxs_sugg_t) --------------------------------------------- */
+
+typedef struct {
+	char *		term;		/* owned by the object, NUL-terminated */
+	size_t		len;
+	unsigned	dist;
+	uint64_t	df;
+} sugg_item_t;
+
+struct nxs_sugg {
+	char *		token;		/* the token after the filters (empty when dropped) */
+	size_t		token_len;
+	bool		dropped;
+	bool		completion;	/* built by nxs_index_complete: `token` is the prefix, the JSON has its own shape */
+	uint64_t	matches;
+	unsigned	count;
+	sugg_item_t	items[];
+};
+
+/* one block: the object, its items, the strings */
+static nxs_sugg_t *
+sugg_build(const char *token, size_t token_len, bool dropped, uint64_t matches, unsigned count,
+    const uint8_t *const *terms, const size_t *lens, const unsigned *dists, const uint64_t *dfs)
+{
+	size_t bytes = sizeof(nxs_sugg_t) + count * sizeof(sugg_item_t) + token_len + 1;
+	nxs_sugg_t *sg;
+	char *str;
+
+	for (unsigned i = 0; i < count; i++) {
+		bytes += lens[i] + 1;
+	}
+	if ((sg = malloc(bytes)) == NULL) {
+		return NULL;
+	}
+	str = (char *)&sg->items[count];
+	sg->token = str;
+	sg->token_len = token_len;
+	memcpy(str, token, token_len);
+	str[token_len] = '\0';
+	str += token_len + 1;
+	sg->dropped = dropped;
+	sg->completion = false;
+	sg->matches = matches;
+	sg->count = count;
+	for (unsigned i = 0; i < count; i++) {
+		sg->items[i].term = str;
+		sg->items[i].len = lens[i];
+		sg->items[i].dist = dists[i];
+		sg->items[i].df = dfs[i];
+		memcpy(str, terms[i], lens[i]);
+		str[lens[i]] = '\0';
+		str += lens[i] + 1;
+	}
+	return sg;
+}
+
+unsigned
+nxs_sugg_count(const nxs_sugg_t *sg)
+{
+	return sg->count;
+}
+
+uint64_t
+nxs_sugg_matches(const nxs_sugg_t *sg)
+{
+	return sg->matches;
+}
+
+bool
+nxs_sugg_dropped(const nxs_sugg_t *sg)
+{
+	return sg->dropped;
+}
+
+bool
+nxs_sugg_get(const nxs_sugg_t *sg, unsigned i, const char **term, size_t *len, unsigned *distance, uint64_t *df)
+{
+	if (i >= sg->count) {
+		return false;
+	}
+	if (term) *term = sg->items[i].term;
+	if (len) *len = sg->items[i].len;
+	if (distance) *distance = sg->items[i].dist;
+	if (df) *df = sg->items[i].df;
+	return true;
+}
+
+void
+nxs_sugg_release(nxs_sugg_t *sg)
+{
+	free(sg);
+}
+
+/* {"token":"...","suggestions":[{"term":"...","distance":D,"df":N},...],"matches":M}; of a completion:
+ * {"prefix":"...","completions":[{"term":"...","df":N},...],"matches":M} */
+char *
+nxs_sugg_tojson(nxs_sugg_t *sg, size_t *len)
+{
+	size_t cap = 96 + 6 * sg->token_len, o = 0;
+	char *s;
+
+	for (unsigned i = 0; i < sg->count; i++) {
+		cap += 64 + 6 * sg->items[i].len;
+	}
+	if ((s = malloc(cap)) == NULL) {
+		return NULL;
+	}
+	o += (size_t)sprintf(s + o, sg->completion ? "{\"prefix\":" : "{\"token\":");
+	o += json_str(s + o, sg->token, sg->token_len);
+	o += (size_t)sprintf(s + o, sg->completion ? ",\"completions\":[" : ",\"suggestions\":[");
+	for (unsigned i = 0; i < sg->count; i++) {
+		o += (size_t)sprintf(s + o, "%s{\"term\":", i ? "," : "");
+		o += json_str(s + o, sg->items[i].term, sg->items[i].len);
+		if (sg->completion) {
+			o += (size_t)sprintf(s + o, ",\"df\":%llu}", (unsigned long long)sg->items[i].df);
+		} else {
+			o += (size_t)sprintf(s + o, ",\"distance\":%u,\"df\":%llu}", sg->items[i].dist,
+			    (unsigned long long)sg->items[i].df);
+		}
+	}
+	o += (size_t)sprintf(s + o, "],\"matches\":%llu}", (unsigned long long)sg->matches);
+	if (len) {
+		*len = o;
+	}
+	return s;
+}
+
+/* ---- the path both calls take: enter, stage, pack, (the device call), build ------------------------- */
+
+/* the strings of one call: what the filters made of them, the kept ones packed for the device, its answers */
+typedef struct {
+	size_t		n;
+	struct lookup_str {
+		char *	val;		/* after the filters (owned) */
+		size_t	len;
+		int	act;		/* 1 = goes to the device, 0 = does not (the caller says what that means),
+					 * < 0 = the filters failed */
+	} *		s;		/* [n] */
+	size_t		nd;		/* strings packed: those with act == 1, in order */
+	uint8_t *	bytes;		/* back to back ... */
+	uint32_t *	off;		/* ... [nd + 1] */
+	uint32_t	*ids, *df;	/* the device's answers: [nd * k], */
+	uint8_t *	dist;		/* [nd * k] (suggest only), */
+	uint32_t	*counts, *matches;	/* [nd] */
+} lookup_t;
+
+static void
+lookup_free(lookup_t *st)
+{
+	for (size_t i = 0; st->s && i < st->n; i++) {
+		free(st->s[i].val);
+	}
+	free(st->s);
+	free(st->off);
+	free(st->bytes);
+	free(st->ids);
+	free(st->df);
+	free(st->dist);
+	free(st->counts);
+	free(st->matches);
+}
+
+/* what comes before the strings are looked at, and after the caller has read its params.  0 / -1 */
+static int
+lookup_enter(nxs_index_t *idx, const char *what, size_t n)
+{
+	nxs_t *nxs = idx->nxs;
+
+	/* (a shard's dictionary and df are collection-wide, its postings are not: a follow-up, include/nxs.h) */
+	if (idx->n_shards) {
+		nxs_decl_err(nxs, NXS_ERR_INVALID, "%s is not available on a doc shard", what);
+		return -1;
+	}
+	if (n > UINT32_MAX / 2) {
+		nxs_decl_err(nxs, NXS_ERR_LIMIT, "batch too large");
+		return -1;
+	}
+	/*
+	 * search.c:309-312, as every search does.  The call is local: with a communicator attached the
+	 * batches in flight can only be finished by all ranks together (resync_before_batch), so while
+	 * some are in flight this rank answers from the snapshot they run on.
+	 */
+	if (!(idx->comm && pend_oldest(idx)) && resync_before_batch(idx) == -1) {
+		return -1;
+	}
+	/* new terms reach the BK image first.  (A batch whose fuzzy pass is still on the device reads the
+	 * image: it was synced for that pass, and nothing can have moved since without finishing the batch --
+	 * should the image be stale all the same, the pass is waited for before it is replaced.) */
+	if (idx->bk_upto != idx->last_id || idx->bk_flags_stale) {
+		(void)late_finish(idx);
+		if (nxs_index_bk_sync(idx) == -1) {
+			return -1;
+		}
+	}
+	return 0;
+}
+
+/* a copy of every string through the index's filters on `stages` (lens: NULL = NUL-terminated).  0 / -1 */
+static int
+lookup_stage(nxs_index_t *idx, const char *const *strings, const size_t *lens, size_t n, unsigned stages,
+    lookup_t *st)
+{
+	st->n = n;
+	if ((st->s = calloc(n ? n : 1, sizeof(*st->s))) == NULL) {
+		goto oom;
+	}
+	for (size_t i = 0; i < n; i++) {
+		struct lookup_str *e = &st->s[i];
+
+		e->len = lens ? lens[i] : strlen(strings[i]);
+		if ((e->val = malloc(e->len + 1)) == NULL) {
+			goto oom;
+		}
+		memcpy(e->val, strings[i], e->len);
+		e->val[e->len] = '\0';
+		e->act = nxs_index_filter(idx, stages, &e->val, &e->len);
+	}
+	return 0;
+oom:
+	nxs_decl_err(idx->nxs, NXS_ERR_SYSTEM, "out of memory");
+	return -1;
+}
+
+/* the strings with act == 1 as the device reads them, and room for its k answers to each.  0 / -1 */
+static int
+lookup_pack(nxs_t *nxs, lookup_t *st, unsigned k)
+{
+	size_t blen = 0, nd = 0;
+
+	for (size_t i = 0; i < st->n; i++) {
+		if (st->s[i].act == 1) {
+			blen += st->s[i].len;
+			nd++;
+		}
+	}
+	if (blen > UINT32_MAX / 2) {
+		nxs_decl_err(nxs, NXS_ERR_LIMIT, "batch too large");
+		return -1;
+	}
+	st->off = malloc((nd + 1) * sizeof(*st->off));
+	st->bytes = malloc(blen + 16);
+	st->ids = malloc((nd * k + 1) * sizeof(*st->ids));
+	st->df = malloc((nd * k + 1) * sizeof(*st->df));
+	st->dist = malloc(nd * k + 1);
+	st->counts = malloc((nd + 1) * sizeof(*st->counts));
+	st->matches = malloc((nd + 1) * sizeof(*st->matches));
+	if (!st->off || !st->bytes || !st->ids || !st->df || !st->dist || !st->counts || !st->matches) {
+		nxs_decl_err(nxs, NXS_ERR_SYSTEM, "out of memory");
+		return -1;
+	}
+	blen = 0;
+	for (size_t i = 0; i < st->n; i++) {
+		if (st->s[i].act == 1) {
+			st->off[st->nd++] = (uint32_t)blen;
+			memcpy(st->bytes + blen, st->s[i].val, st->s[i].len);
+			blen += st->s[i].len;
+		}
+	}
+	st->off[st->nd] = (uint32_t)blen;
+	return 0;
+}
+
+/*
+ * String i's object from the device's answer to packed string *nd (stepped here), or its failure: NULL with
+ * errs[i] and the error set.  `noun` names the string in messages.  dist == NULL: the device sends no
+ * distances -- the terms start with the string, and the pair's true Levenshtein distance is what they add.
+ */
+static nxs_sugg_t *
+lookup_build(nxs_index_t *idx, const lookup_t *st, size_t i, size_t *nd, unsigned k, const uint8_t *dist,
+    const char *noun, nxs_err_t *errs)
+{
+	const uint8_t *terms[NXS_SUGGEST_MAX];
+	size_t tlens[NXS_SUGGEST_MAX];
+	unsigned dists[NXS_SUGGEST_MAX];
+	uint64_t dfs[NXS_SUGGEST_MAX];
+	nxs_err_t code = NXS_ERR_FATAL;
+	nxs_sugg_t *sg;
+	size_t at;
+	unsigned c;
+
+	if (st->s[i].act < 0) {
+		/* FILT_ERROR: what fails a query (search.c:199-203) fails this string */
+		nxs_decl_err(idx->nxs, code, "the filters failed on %s %zu", noun, i);
+		goto fail;
+	}
+	at = (*nd)++;
+	/* (count = min(k, matches) is the device's contract, k <= NXS_SUGGEST_MAX the params': the arrays hold it) */
+	c = st->counts[at] <= k ? st->counts[at] : k;
+	for (unsigned j = 0; j < c; j++) {
+		const uint32_t id = st->ids[at * k + j];
+
+		if (id < 1 || id > idx->last_id || (!dist && idx->terms[id].len < st->s[i].len)) {
+			nxs_decl_err(idx->nxs, code, "the device named an unknown term for %s %zu", noun, i);
+			goto fail;
+		}
+		terms[j] = idx->terms[id].val;
+		tlens[j] = idx->terms[id].len;
+		dists[j] = dist ? dist[at * k + j] : (unsigned)(tlens[j] - st->s[i].len);
+		dfs[j] = st->df[at * k + j];
+	}
+	if ((sg = sugg_build(st->s[i].val, st->s[i].len, false, st->matches[at], c, terms, tlens, dists, dfs)) != NULL) {
+		return sg;
+	}
+	code = NXS_ERR_SYSTEM;
+	nxs_decl_err(idx->nxs, code, "out of memory");
+fail:
+	if (errs) {
+		errs[i] = code;
+	}
+	return NULL;
+}
+
+/* ---- spelling suggestions (nxs_index_suggest) ---------------------------------------- */
+
+/* `key`: how many terms a call returns (1..NXS_SUGGEST_MAX, default 5) */
+static int
+get_limit_param(nxs_t *nxs, const nxs_params_t *params, const char *key, unsigned *k)
+{
+	uint64_t v;
+
+	*k = 5;
+	if (params && nxs_params_get_uint(params, key, &v) == 0) {
+		if (v < 1 || v > NXS_SUGGEST_MAX) {
+			nxs_decl_err(nxs, NXS_ERR_INVALID, "invalid %s (1..%d)", key, NXS_SUGGEST_MAX);
+			return -1;
+		}
+		*k = (unsigned)v;
+	}
+	return 0;
+}
+
+/* "suggest_limit", "suggest_maxdist" (1 or 2, default 2) */
+static int
+get_suggest_params(nxs_t *nxs, const nxs_params_t *params, unsigned *k, unsigned *maxdist)
+{
+	uint64_t v;
+
+	*maxdist = LEVDIST_TOLERANCE;
+	if (get_limit_param(nxs, params, "suggest_limit", k) == -1) {
+		return -1;
+	}
+	if (params && nxs_params_get_uint(params, "suggest_maxdist", &v) == 0) {
+		if (v < 1 || v > LEVDIST_TOLERANCE) {
+			nxs_decl_err(nxs, NXS_ERR_INVALID, "invalid suggest_maxdist (1 or 2)");
+			return -1;
+		}
+		*maxdist = (unsigned)v;
+	}
+	return 0;
+}
+
+/* lens: NULL = the strings are NUL-terminated */
+static int
+suggest_run(nxs_index_t *idx, nxs_params_t *params, const char *const *tokens, const size_t *lens, size_t n,
+    nxs_sugg_t **out, nxs_err_t *errs)
+{
+	nxs_t *nxs = idx->nxs;
+	lookup_t st = { 0 };
+	unsigned k, maxdist;
+	size_t nd = 0;
+	int ret = -1, failed = 0;
+
+	nxs_clear_error(nxs);
+	outs_clear(out, errs, n);
+	if (get_suggest_params(nxs, params, &k, &maxdist) == -1 || lookup_enter(idx, "suggest", n) == -1) {
+		return -1;
+	}
+	/* the filters a query token goes through (tokenizer.c:205-227): normalizer, stop words, stemmer */
+	if (lookup_stage(idx, tokens, lens, n, ~0u, &st) == -1 || lookup_pack(nxs, &st, k) == -1) {
+		goto out;
+	}
+	if (st.nd && nxsgpu_suggest(idx->dev, st.bytes, st.off, (uint32_t)st.nd, maxdist, k, st.ids, st.dist, st.df,
+	    st.counts, st.matches) != 0) {
+		nxs_decl_err(nxs, NXS_ERR_FATAL, "device suggest pass failed: %s", nxsgpu_last_error());
+		goto out;
+	}
+	for (size_t i = 0; i < n; i++) {
+		if (st.s[i].act != 0) {
+			out[i] = lookup_build(idx, &st, i, &nd, k, st.dist, "token", errs);
+		} else if ((out[i] = sugg_build("", 0, true, 0, 0, NULL, NULL, NULL, NULL)) == NULL) {
+			/* (the filters dropped the token: an object that says so) */
+			if (errs) {
+				errs[i] = NXS_ERR_SYSTEM;
+			}
+			nxs_decl_err(nxs, NXS_ERR_SYSTEM, "out of memory");
+		}
+		failed += !out[i];
+	}
+	ret = failed;
+out:
+	lookup_free(&st);
+	return ret;
+}
+
+int
+nxs_index_suggest_batch(nxs_index_t *idx, nxs_params_t *params, const char *const *tokens, size_t n,
+    nxs_sugg_t **out, nxs_err_t *errs)
+{
+	return suggest_run(idx, params, tokens, NULL, n, out, errs);
+}
+
+nxs_sugg_t *
+nxs_index_suggest(nxs_index_t *idx, nxs_params_t *params, const char *token, size_t len)
+{
+	nxs_sugg_t *sg = NULL;
+
+	/* (one string: the call fails exactly when it leaves no object) */
+	(void)suggest_run(idx, params, &token, &len, 1, &sg, NULL);
+	return sg;
+}
+
+/* ---- prefix completion (nxs_index_complete) ------------------------------------------- */
+
+/* lens: NULL = the strings are NUL-terminated */
+static int
+complete_run(nxs_index_t *idx, nxs_params_t *params, const char *const *prefixes, const size_t *lens, size_t n,
+    nxs_sugg_t **out, nxs_err_t *errs)
+{
+	nxs_t *nxs = idx->nxs;
+	lookup_t st = { 0 };
+	unsigned k;
+	size_t nd = 0;
+	int ret = -1, failed = 0;
+
+	nxs_clear_error(nxs);
+	outs_clear(out, errs, n);
+	if (get_limit_param(nxs, params, "complete_limit", &k) == -1 || lookup_enter(idx, "complete", n) == -1) {
+		return -1;
+	}
+	/* a prefix is a fragment, not a word: the normalizer / lowercase stage only (nxs_filters_run_stages) */
+	if (lookup_stage(idx, prefixes, lens, n, NXS_FSTAGE_NORMALIZER, &st) == -1) {
+		goto out;
+	}
+	for (size_t i = 0; i < n; i++) {
+		if (st.s[i].act == 1 && st.s[i].len == 0) {
+			st.s[i].act = 0;		/* empty before or after normalisation: NXS_ERR_INVALID below */
+		}
+	}
+	if (lookup_pack(nxs, &st, k) == -1) {
+		goto out;
+	}
+	if (st.nd && nxsgpu_complete(idx->dev, st.bytes, st.off, (uint32_t)st.nd, k, st.ids, st.df, st.counts,
+	    st.matches) != 0) {
+		nxs_decl_err(nxs, NXS_ERR_FATAL, "device complete pass failed: %s", nxsgpu_last_error());
+		goto out;
+	}
+	for (size_t i = 0; i < n; i++) {
+		if (st.s[i].act != 0) {
+			out[i] = lookup_build(idx, &st, i, &nd, k, NULL, "prefix", errs);
+		} else {
+			if (errs) {
+				errs[i] = NXS_ERR_INVALID;
+			}
+			nxs_decl_err(nxs, NXS_ERR_INVALID, "empty prefix");
+		}
+		if (out[i]) {
+			out[i]->completion = true;
+		}
+		failed += !out[i];
+	}
+	ret = failed;
+out:
+	lookup_free(&st);
+	return ret;
+}
+
+int
+nxs_index_complete_batch(nxs_index_t *idx, nxs_params_t *params, const char *const *prefixes, size_t n,
+    nxs_sugg_t **out, nxs_err_t *errs)
+{
+	return complete_run(idx, params, prefixes, NULL, n, out, errs);
+}
+
+nxs_sugg_t *
+nxs_index_complete(nxs_index_t *idx, nxs_params_t *params, const char *prefix, size_t len)
+{
+	nxs_sugg_t *sg = NULL;
+
+	(void)complete_run(idx, params, &prefix, &len, 1, &sg, NULL);	/* (as nxs_index_suggest) */
+	return sg;
+}
+
+#ifdef NXS_TEST_HOOKS
+/* the parameters as nxs_index_complete / a search read them: 0, or -1 with the error declared */
+int
+nxs_test_complete_params(nxs_t *nxs, nxs_params_t *params, unsigned *k, int *prefixmatch, unsigned *prefix_limit)
+{
+	nxs_index_t fake = { .nxs = nxs };
+	search_params_t sp;
+
+	nxs_clear_error(nxs);
+	if (get_limit_param(nxs, params, "complete_limit", k) == -1 || get_search_params(&fake, params, &sp) == -1) {
+		return -1;
+	}
+	*prefixmatch = sp.prefixmatch;
+	*prefix_limit = sp.prefix_limit;
+	return 0;
+}
+
+/* an nxs_sugg_t of the completion kind built by hand */
+nxs_sugg_t *
+nxs_test_compl_build(const char *prefix, size_t prefix_len, uint64_t matches, unsigned count,
+    const uint8_t *const *terms, const size_t *lens, const uint64_t *dfs)
+{
+	unsigned dists[NXS_SUGGEST_MAX];
+	nxs_sugg_t *sg;
+
+	for (unsigned i = 0; i < count && i < NXS_SUGGEST_MAX; i++) {
+		dists[i] = (unsigned)(lens[i] - prefix_len);
+	}
+	if ((sg = sugg_build(prefix, prefix_len, false, matches, count, terms, lens, dists, dfs)) != NULL) {
+		sg->completion = true;
+	}
+	return sg;
+}
+
+/* the parameters as nxs_index_suggest reads them: 0, or -1 with the error declared */
+int
+nxs_test_suggest_params(nxs_t *nxs, nxs_params_t *params, unsigned *k, unsigned *maxdist)
+{
+	nxs_clear_error(nxs);
+	return get_suggest_params(nxs, params, k, maxdist);
+}
+
+/* an nxs_sugg_t built by hand (the accessors and the JSON writer without an index) */
+nxs_sugg_t *
+nxs_test_sugg_build(const char *token, size_t token_len, bool dropped, uint64_t matches, unsigned count,
+    const uint8_t *const *terms, const size_t *lens, const unsigned *dists, const uint64_t *dfs)
+{
+	return sugg_build(token, token_len, dropped, matches, count, terms, lens, dists, dfs);
+}
+#endif /* NXS_TEST_HOOKS */

@@ -450,19 +450,11 @@ prepare_prefix(const nxs_index_t *idx, qprep_t *out, size_t item, const char *st
 		out->errmsg = strdup("out of memory");
 		return -1;
 	}
-	if (idx && idx->filters) {
-		if (nxs_filters_run_stages(idx->filters, NXS_FSTAGE_NORMALIZER, &val, &len) < 0) {
-			free(val);
-			out->errcode = NXS_ERR_FATAL;
-			out->errmsg = strdup("query_prepare() failed");
-			return -1;
-		}
-	} else if (idx && idx->lowercase) {
-		for (size_t c = 0; c < len; c++) {
-			if (val[c] >= 'A' && val[c] <= 'Z') {
-				val[c] += 32;
-			}
-		}
+	if (idx && nxs_index_filter(idx, NXS_FSTAGE_NORMALIZER, &val, &len) < 0) {
+		free(val);
+		out->errcode = NXS_ERR_FATAL;
+		out->errmsg = strdup("query_prepare() failed");
+		return -1;
 	}
 	if (len == 0) {
 		free(val);
@@ -544,9 +536,9 @@ nxs_query_prepare_px(const nxs_index_t *idx, const char *query, bool prefixmatch
 		}
 		/* tokenize_value: the index's filter pipeline on the leaf string
 		 * (tokenizer.c:205-227; nxs_filters.c) */
-		if (idx && idx->filters) {
+		if (idx) {
 			char *fv = val;
-			const int act = nxs_filters_run(idx->filters, &fv, &len);
+			const int act = nxs_index_filter(idx, ~0u, &fv, &len);
 
 			if (act == 1 && fv != val) {
 				/* the ICU path replaced the string: keep a copy in the arena
@@ -575,13 +567,6 @@ nxs_query_prepare_px(const nxs_index_t *idx, const char *query, bool prefixmatch
 				out->errmsg = strdup("query_prepare() failed");
 				free(ff);
 				return;
-			}
-		} else if (idx && idx->lowercase) {
-			/* (host-only tests without a pipeline object) */
-			for (size_t c = 0; c < len; c++) {
-				if (val[c] >= 'A' && val[c] <= 'Z') {
-					val[c] += 32;
-				}
 			}
 		}
 		for (j = 0; j < out->n_tokens; j++) {

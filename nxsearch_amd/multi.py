@@ -8,7 +8,7 @@ token_count and df are identical on all replicas, so no statistics are
 exchanged), and ONE RCCL all-gather of the ranks' record blocks -- fixed-size
 per-query records `count u32 | flags u32 | k x u64 doc id | k x f32 score`,
 128 B at k = 10 -- reassembles the batch on every rank over xGMI.  All of it
-lives behind the C ABI (csrc/nxs_api.c, nxs_gpu.hip); this module only
+lives behind the C ABI (csrc/nxs_batch.c, nxs_gpu_comm.hip); this module only
 distributes the communicator's unique id with whatever channel the
 application already has (here: torch.distributed) and wraps the test hooks.
 The reference has no counterpart: it scales by running independent worker
@@ -54,7 +54,7 @@ def attach(nxs, index, rank, world, dist=None, device=None):
     index.shard(rank, world, uid)
 
 
-# ---- test hooks (CPU-side stand-ins; see nxs_api.c "Sharding without a second GPU")
+# ---- test hooks (CPU-side stand-ins; see nxs_batch.c "Sharding without a second GPU")
 
 def emulate(index, rank, world):
     """The index plays rank `rank` of `world` without a collective (0: off)."""
