@@ -47,7 +47,8 @@ typedef enum {
 nxs_err_t	nxs_get_error(const nxs_t *, const char **);	/* nxs.h:48 */
 
 /* Parameters (nxs.h:54-67); the query path reads limit / algo / fuzzymatch / total / prefixmatch /
- * prefix_limit / explain, nxs_index_suggest reads suggest_limit / suggest_maxdist, nxs_index_complete complete_limit */
+ * prefix_limit / explain / wildcardmatch / wildcard_terms, nxs_index_suggest reads suggest_limit /
+ * suggest_maxdist, nxs_index_complete complete_limit, nxs_index_wildcard wildcard_limit */
 struct nxs_params;
 typedef struct nxs_params nxs_params_t;
 
@@ -234,6 +235,55 @@ void		nxs_sugg_release(nxs_sugg_t *);
 nxs_sugg_t *	nxs_index_complete(nxs_index_t *, nxs_params_t *, const char *prefix, size_t len);
 int		nxs_index_complete_batch(nxs_index_t *, nxs_params_t *,
 		    const char *const *prefixes, size_t n,
+		    nxs_sugg_t **out, nxs_err_t *errs);
+
+/*
+ * Wildcard term matching (new; the reference's lexer takes `*` and `?` for ordinary bytes of a free-form
+ * string, so `micro*ft` is looked up verbatim there).
+ *
+ * A PATTERN is a byte string: `*` matches any run of bytes, the empty run included; `?` matches exactly one
+ * byte (byte-wise, as the Levenshtein distance and the prefixes here are); every other byte matches itself.
+ * There are no escapes and no classes.  A term matches when the whole term matches the whole pattern.
+ * Normalisation: the pattern is cut at its metacharacters, each literal piece takes the normalizer /
+ * lowercase stage of the index's pipeline only (the rule of a prefix, for the same reason: a fragment is not
+ * a word), the pieces are put back together and runs of `*` collapse to one.  A pattern that holds no literal
+ * byte after normalisation (`*`, `??`, `*?*`) is not served: in a call it is NXS_ERR_INVALID "empty
+ * pattern", in a query the leaf is the empty set, as a prefix that normalises to nothing is.  A normalised
+ * pattern longer than NXS_WILD_MAXLEN (255) bytes is NXS_ERR_INVALID "wildcard pattern too long"; in a batch
+ * that error belongs to the query (string) that holds the pattern -- errs[i] -- not to the batch.
+ * The ELIGIBLE terms are the dictionary terms that have a posting in a live doc of the current snapshot
+ * (df > 0, the rule of suggestions and completions) and match.  Their ORDER is df descending, then term id
+ * ascending: a total order.  `matches` is the exact number of eligible terms, however large.
+ *
+ * nxs_index_wildcard: the first min(k, matches) eligible terms of `pattern`, k = "wildcard_limit" (uint,
+ * 1..NXS_SUGGEST_MAX, default 5; out of range: NXS_ERR_INVALID naming the key), as an nxs_sugg_t:
+ * nxs_sugg_get reports distance = len(term) - the number of literal bytes of the pattern; nxs_sugg_matches
+ * is exact; nxs_sugg_dropped is false.  nxs_sugg_tojson of such an object:
+ *   {"pattern":"<normalised pattern>","terms":[{"term":"...","df":12},...],"matches":7}
+ * with the escaping rules above.  nxs_index_wildcard_batch: as nxs_index_suggest_batch.  Everything else is
+ * nxs_index_complete's: the call re-syncs with the files, is allowed with batches or a pending fuzzy pass in
+ * flight, is local under a communicator, and on a handle from nxs_index_open_shard fails with
+ * NXS_ERR_INVALID "wildcard is not available on a doc shard".
+ *
+ * Wildcard leaves in queries: "wildcardmatch" (bool, default FALSE) and "wildcard_terms" (uint, 1..32,
+ * default 8; out of range: NXS_ERR_INVALID naming the key).  With wildcardmatch false or absent nothing
+ * changes: `*` and `?` stay ordinary bytes of a free-form string.  With it, a leaf that comes from a
+ * free-form (never a quoted) string is a wildcard leaf when it holds a `*` or `?` and at least one other
+ * byte.  One exception keeps "prefixmatch" as it is: with that flag set too, a literal followed by a single
+ * trailing `*` and no other metacharacter is the prefix leaf it is today, with prefix_limit.  The query
+ * behaves EXACTLY as the query in which the leaf is (e1 OR e2 OR ... OR em), e1..em the first
+ * min(wildcard_terms, matches) eligible terms in the order above, each already resolved (no filters, no fuzzy
+ * lookup): doc set, token set and order, ties, "total" and "explain" follow the rewritten query.  A wildcard
+ * leaf is never fuzzy-matched; m = 0 makes it the empty set; the expansions count towards the existing token
+ * limits.  Served by nxs_index_search, nxs_index_search_batch[_begin/_end] (the batch's distinct patterns are
+ * resolved by one blocking device pass in _begin), nxs_index_plan_batch and query-sharded batches (the
+ * replicas hold one dictionary and df).  The nxs_docshard_* searches refuse a batch that holds a wildcard
+ * leaf: -1 and NXS_ERR_INVALID "wildcardmatch is not available on a doc shard".
+ */
+#define	NXS_WILD_MAXLEN		255
+nxs_sugg_t *	nxs_index_wildcard(nxs_index_t *, nxs_params_t *, const char *pattern, size_t len);
+int		nxs_index_wildcard_batch(nxs_index_t *, nxs_params_t *,
+		    const char *const *patterns, size_t n,
 		    nxs_sugg_t **out, nxs_err_t *errs);
 
 /*

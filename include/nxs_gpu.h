@@ -25,6 +25,9 @@
  *   nxsgpu_complete      (new: no seam in the reference) every live term that
  *                           begins with a prefix, ranked by df -- a range of
  *                           the terms' byte order.
+ *   nxsgpu_wildcard      (new: no seam in the reference) every live term that
+ *                           matches a `*` / `?` pattern, ranked by df -- a scan
+ *                           of the range its literal head selects.
  */
 #ifndef NXS_GPU_H
 #define NXS_GPU_H
@@ -350,6 +353,37 @@ void		nxsgpu_suggest_profile(nxsgpu_index_t *, double out[NXSGPU_SUGGEST_PROF], 
 int		nxsgpu_complete(nxsgpu_index_t *, const uint8_t *bytes, const uint32_t *off, uint32_t n, uint32_t k,
 		    uint32_t *term_ids, uint32_t *df, uint32_t *counts, uint32_t *matches);	/* rows [n][k]; 0 / -1 */
 void		nxsgpu_complete_profile(nxsgpu_index_t *, double out[NXSGPU_COMPLETE_PROF], int reset);
+
+/*
+ * ---- wildcard term matching ---------------------------------------------------------
+ *
+ * nxsgpu_wildcard: for each of n patterns (bytes off[i] .. off[i + 1], already normalised, at most 255 bytes:
+ * `*` any run of bytes, `?` one byte, every other byte itself; csrc/nxs_wild.h) the ELIGIBLE terms -- a posting
+ * in a live doc (df > 0) and the whole term matches the whole pattern -- in the order df descending, term id
+ * ascending.  Rows of k (1..32) entries as nxsgpu_complete's: term_ids / df [n][k], counts[i] = min(k,
+ * matches[i]), matches[i] the exact number of eligible terms, however large.
+ *
+ * The pass reads nxsgpu_complete's order of the live terms (built by whichever call comes first, rebuilt when
+ * the generation has moved) and builds none of its own: the pattern's literal head selects a range of it by
+ * the same two binary searches (all of it when the pattern begins with a metacharacter), k_wc_match scans
+ * the range -- (part of a range, pattern) per workgroup, at most NXS_GPU_WILD_PARTS (default 64) parts, a
+ * running top-k per workgroup in LDS, matches counted by ballot -- and k_wc_merge selects the k best of a
+ * pattern's parts.  Device memory is n x parts x k keys, never a list of matches; a batch whose partial lists
+ * would exceed 64 MiB is cut into chunks of patterns.  Stream, workspace and concurrency as nxsgpu_complete;
+ * blocking.  Under NXS_GPU_WILDCARD=host (the cross-check route) every pattern is ranked on the host over a
+ * copy of the BK image.  0 / -1.
+ *
+ * nxsgpu_wildcard_profile: since the last reset -- out[0] device passes (chunks), out[1] their HIP-event ms,
+ * out[2] the range searches, out[3] k_wc_match, out[4] k_wc_merge (out[1..4] with nxsgpu_set_profiling only),
+ * out[6] patterns answered on the host, out[8] patterns answered on the device; not reset: out[5] entries in
+ * the order (or the host copy), out[7] builds of the order or of the host copy since the index was created
+ * (nxsgpu_complete's builds included: the two calls share them, and each route builds its own once per
+ * generation).
+ */
+#define	NXSGPU_WILDCARD_PROF	10
+int		nxsgpu_wildcard(nxsgpu_index_t *, const uint8_t *bytes, const uint32_t *off, uint32_t n, uint32_t k,
+		    uint32_t *term_ids, uint32_t *df, uint32_t *counts, uint32_t *matches);	/* rows [n][k]; 0 / -1 */
+void		nxsgpu_wildcard_profile(nxsgpu_index_t *, double out[NXSGPU_WILDCARD_PROF], int reset);
 
 /*
  * ---- explanations -------------------------------------------------------------------

@@ -92,6 +92,7 @@ NXS_H_SYMBOLS = [
     "nxs_index_suggest", "nxs_index_suggest_batch", "nxs_sugg_count", "nxs_sugg_matches", "nxs_sugg_dropped",
     "nxs_sugg_get", "nxs_sugg_tojson", "nxs_sugg_release",
     "nxs_index_complete", "nxs_index_complete_batch",
+    "nxs_index_wildcard", "nxs_index_wildcard_batch",
     "nxs_resp_tokens", "nxs_resp_token", "nxs_resp_explain",
 ]
 # csrc/nxs_hooks.h: test hooks + bench accessors, only in builds with -DNXS_TEST_HOOKS (the default)
@@ -100,6 +101,8 @@ NXS_HOOK_SYMBOLS = ["nxs_index_device", "nxs_index_host_profile", "nxs_index_sha
                     "nxs_test_suggest_host", "nxs_test_suggest_params", "nxs_test_sugg_build",
                     "nxs_test_complete_host", "nxs_test_complete_params", "nxs_test_compl_build",
                     "nxs_test_prefix_query", "nxs_test_filter_prefix",
+                    "nxs_test_wild_match", "nxs_test_wild_match_inl", "nxs_test_wild_host", "nxs_test_wild_params",
+                    "nxs_test_wild_normalize", "nxs_test_wild_build", "nxs_test_wild_query",
                     "nxs_test_explain_params", "nxs_test_resp_build", "nxs_test_explain_search",
                     "nxs_test_explain_ordinal"]
 NXS_GPU_H_SYMBOLS = [
@@ -121,6 +124,7 @@ NXS_GPU_H_SYMBOLS = [
     "nxsgpu_batch_end_totals", "nxsgpu_count_tile_widths", "nxsgpu_count_profile",
     "nxsgpu_suggest", "nxsgpu_suggest_profile",
     "nxsgpu_complete", "nxsgpu_complete_profile",
+    "nxsgpu_wildcard", "nxsgpu_wildcard_profile",
     "nxsgpu_explain", "nxsgpu_explain_profile",
 ]
 
@@ -207,6 +211,10 @@ def lib():
     L.nxs_index_complete.argtypes = [vp, vp, cp, C.c_size_t]
     L.nxs_index_complete_batch.restype = C.c_int
     L.nxs_index_complete_batch.argtypes = [vp, vp, C.POINTER(cp), C.c_size_t, C.POINTER(vp), C.POINTER(C.c_int)]
+    L.nxs_index_wildcard.restype = vp
+    L.nxs_index_wildcard.argtypes = [vp, vp, cp, C.c_size_t]
+    L.nxs_index_wildcard_batch.restype = C.c_int
+    L.nxs_index_wildcard_batch.argtypes = [vp, vp, C.POINTER(cp), C.c_size_t, C.POINTER(vp), C.POINTER(C.c_int)]
     L.nxs_sugg_count.restype = C.c_uint
     L.nxs_sugg_count.argtypes = [vp]
     L.nxs_sugg_matches.restype = C.c_uint64
@@ -268,6 +276,12 @@ def lib():
                                   C.POINTER(C.c_uint32)]
     L.nxsgpu_complete_profile.restype = None
     L.nxsgpu_complete_profile.argtypes = [vp, C.POINTER(C.c_double), C.c_int]
+    L.nxsgpu_wildcard.restype = C.c_int
+    L.nxsgpu_wildcard.argtypes = [vp, cp, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32,
+                                  C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                  C.POINTER(C.c_uint32)]
+    L.nxsgpu_wildcard_profile.restype = None
+    L.nxsgpu_wildcard_profile.argtypes = [vp, C.POINTER(C.c_double), C.c_int]
     L.nxsgpu_explain_profile.restype = None
     L.nxsgpu_explain_profile.argtypes = [vp, C.POINTER(C.c_double), C.c_int]
     # host-only test hooks
@@ -351,10 +365,10 @@ class Nxs:
         return Index(self, h)
 
     def docshard_search_batch(self, shards, queries, limit=None, algo=None, fuzzymatch=None, total=False,
-                              prefixmatch=None, explain=False):
+                              prefixmatch=None, explain=False, wildcardmatch=None):
         """nxs_docshard_search_batch(): one batch over all shards, merged exactly.
         total: every result list also carries `.total` (the sum of the shards' counts).
-        (prefixmatch: a batch with a prefix leaf is refused -- NXS_ERR_INVALID.)
+        (prefixmatch / wildcardmatch: a batch with a prefix / wildcard leaf is refused -- NXS_ERR_INVALID.)
         explain: every list carries `.tokens` and `.explain` (each row from the shard that holds the doc)."""
         L = lib()
         L.nxs_docshard_search_batch.restype = C.c_int
@@ -366,7 +380,7 @@ class Nxs:
         qs = (C.c_char_p * max(n, 1))(*[_b(q) for q in queries])
         resps = (C.c_void_p * max(n, 1))()
         errs = (C.c_int * max(n, 1))()
-        p = _make_params(limit, algo, fuzzymatch, total, prefixmatch, explain=explain)
+        p = _make_params(limit, algo, fuzzymatch, total, prefixmatch, explain=explain, wildcardmatch=wildcardmatch)
         try:
             r = L.nxs_docshard_search_batch(hs, len(shards), p, qs, n, resps, errs)
         finally:
@@ -589,9 +603,9 @@ def _suggest_params(limit=None, maxdist=None):
 
 
 def _make_params(limit=None, algo=None, fuzzymatch=None, total=False, prefixmatch=None, prefix_limit=None,
-                 explain=False):
+                 explain=False, wildcardmatch=None, wildcard_terms=None):
     if limit is None and algo is None and fuzzymatch is None and not total and prefixmatch is None \
-            and prefix_limit is None and not explain:
+            and prefix_limit is None and not explain and wildcardmatch is None and wildcard_terms is None:
         return None
     L = lib()
     p = L.nxs_params_create()
@@ -609,6 +623,10 @@ def _make_params(limit=None, algo=None, fuzzymatch=None, total=False, prefixmatc
         L.nxs_params_set_uint(p, b"prefix_limit", prefix_limit)
     if explain:
         L.nxs_params_set_bool(p, b"explain", True)
+    if wildcardmatch is not None:
+        L.nxs_params_set_bool(p, b"wildcardmatch", bool(wildcardmatch))
+    if wildcard_terms is not None:
+        L.nxs_params_set_uint(p, b"wildcard_terms", wildcard_terms)
     return p
 
 
@@ -655,12 +673,14 @@ class Index:
         return lib().nxs_index_device(self._h)
 
     def search(self, query, limit=None, algo=None, fuzzymatch=None, json=False, params_json=None, total=False,
-               prefixmatch=None, prefix_limit=None, explain=False):
+               prefixmatch=None, prefix_limit=None, explain=False, wildcardmatch=None, wildcard_terms=None):
         """nxs_index_search(): -> [(doc_id, score), ...] (or the JSON text).
         params_json: the parameters as the Lua binding passes them (nxs_params_fromjson).
         total: also count the matches -- the list then carries `.total` (the JSON a "total" member).
         prefixmatch: a free-form leaf `term*` stands for the OR of its `prefix_limit` (1..32, default 8) best
         completions.
+        wildcardmatch: a free-form leaf with a `*` / `?` (and another byte) stands for the OR of its
+        `wildcard_terms` (1..32, default 8) best matching terms.
         explain: the list also carries `.tokens` and `.explain` (class Results; the JSON "terms" / "tokens")."""
         L = lib()
         if params_json is not None:
@@ -669,7 +689,7 @@ class Index:
             if not p:
                 self.nxs._raise()
         else:
-            p = _make_params(limit, algo, fuzzymatch, total, prefixmatch, prefix_limit, explain)
+            p = _make_params(limit, algo, fuzzymatch, total, prefixmatch, prefix_limit, explain, wildcardmatch, wildcard_terms)
         q = _b(query)
         try:
             resp = L.nxs_index_search(self._h, p, q, len(q))
@@ -687,7 +707,7 @@ class Index:
             L.nxs_resp_release(resp)
 
     def search_batch(self, queries, limit=None, algo=None, fuzzymatch=None, total=False,
-                     prefixmatch=None, prefix_limit=None, explain=False):
+                     prefixmatch=None, prefix_limit=None, explain=False, wildcardmatch=None, wildcard_terms=None):
         """nxs_index_search_batch(): list of result lists; a failed query
         yields an NxsError instance in its slot.  total: every list carries `.total`; explain: `.tokens` and
         `.explain`."""
@@ -696,7 +716,7 @@ class Index:
         qs = (C.c_char_p * n)(*[_b(q) for q in queries])
         resps = (C.c_void_p * n)()
         errs = (C.c_int * n)()
-        p = _make_params(limit, algo, fuzzymatch, total, prefixmatch, prefix_limit, explain)
+        p = _make_params(limit, algo, fuzzymatch, total, prefixmatch, prefix_limit, explain, wildcardmatch, wildcard_terms)
         try:
             r = L.nxs_index_search_batch(self._h, p, qs, n, resps, errs)
         finally:
@@ -714,14 +734,15 @@ class Index:
         return out
 
     def search_batch_begin(self, queries, limit=None, algo=None, fuzzymatch=None, total=False,
-                           prefixmatch=None, prefix_limit=None, explain=False):
+                           prefixmatch=None, prefix_limit=None, explain=False, wildcardmatch=None,
+                           wildcard_terms=None):
         """nxs_index_search_batch_begin(): queue a batch (at most NXS_BATCHES_INFLIGHT = 4 in flight).
         total: the lists search_batch_end() returns for this batch carry `.total`; explain: `.tokens` and
         `.explain`."""
         L = lib()
         n = len(queries)
         qs = (C.c_char_p * max(n, 1))(*[_b(q) for q in queries])
-        p = _make_params(limit, algo, fuzzymatch, total, prefixmatch, prefix_limit, explain)
+        p = _make_params(limit, algo, fuzzymatch, total, prefixmatch, prefix_limit, explain, wildcardmatch, wildcard_terms)
         try:
             r = L.nxs_index_search_batch_begin(self._h, p, qs, n)
         finally:
@@ -805,14 +826,15 @@ class Index:
         """Re-read the NXS_GPU_* switches (parsed once at open); tests/tools."""
         lib().nxsgpu_index_reconfigure(self.device)
 
-    def plan_batch(self, queries, limit=None, algo=None, fuzzymatch=None, prefixmatch=None, prefix_limit=None):
+    def plan_batch(self, queries, limit=None, algo=None, fuzzymatch=None, prefixmatch=None, prefix_limit=None,
+                   wildcardmatch=None, wildcard_terms=None):
         """nxs_index_plan_batch(): -> (ctypes array of GpuQuery, [err codes])."""
         L = lib()
         n = len(queries)
         qs = (C.c_char_p * n)(*[_b(q) for q in queries])
         plans = (GpuQuery * max(n, 1))()
         errs = (C.c_int * max(n, 1))()
-        p = _make_params(limit, algo, fuzzymatch, False, prefixmatch, prefix_limit)
+        p = _make_params(limit, algo, fuzzymatch, False, prefixmatch, prefix_limit, False, wildcardmatch, wildcard_terms)
         try:
             r = L.nxs_index_plan_batch(self._h, p, qs, n, plans, errs)
         finally:
@@ -917,6 +939,29 @@ class Index:
         lib().nxsgpu_complete_profile(self.device, out, 1 if reset else 0)
         return {"passes": int(out[0]), "ms": out[1], "range_ms": out[2], "select_ms": out[3], "build_ms": out[4],
                 "entries": int(out[5]), "host_prefixes": int(out[6]), "builds": int(out[7])}
+
+    def wildcard(self, patterns, limit=None, json=False):
+        """nxs_index_wildcard_batch(): for every pattern (`*` any run of bytes, `?` one byte; its literal pieces
+        normalised, never stemmed or dropped as stop words) the dictionary terms that match it and that some
+        live doc holds, best `limit` (1..32, default 5) by df descending, then term id -> a list of
+        Suggestions, one per pattern, entries (term, distance = len(term) - the pattern's literal bytes, df),
+        `.matches` exact (an NxsError instance in the slot of a pattern that failed: one without a literal
+        byte, or longer than 255 bytes); json: their JSON texts."""
+        p = None
+        if limit is not None:
+            p = lib().nxs_params_create()
+            lib().nxs_params_set_uint(p, b"wildcard_limit", limit)
+        return self._lookup_batch(lib().nxs_index_wildcard_batch, patterns, p, "pattern", json)
+
+    def wildcard_profile(self, reset=False):
+        """nxsgpu_wildcard_profile(): device passes and their HIP-event times per kernel (profiling on),
+        patterns answered on the host / on the device; the entries of the term order and its builds since the
+        index was opened (never reset)."""
+        out = (C.c_double * 10)()
+        lib().nxsgpu_wildcard_profile(self.device, out, 1 if reset else 0)
+        return {"passes": int(out[0]), "ms": out[1], "range_ms": out[2], "match_ms": out[3], "merge_ms": out[4],
+                "entries": int(out[5]), "host_patterns": int(out[6]), "builds": int(out[7]),
+                "device_patterns": int(out[8])}
 
     def explain_profile(self, reset=False):
         """nxsgpu_explain_profile(): explain passes, HIP-event ms of k_explain (profiling on), (result, token)

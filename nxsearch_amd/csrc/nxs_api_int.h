@@ -54,6 +54,8 @@ typedef struct {
 	bool		total;		/* "total": also count the matches (nxs_resp_total) */
 	bool		prefixmatch;	/* "prefixmatch": a free-form leaf `term*` stands for its best completions */
 	unsigned	prefix_limit;	/* "prefix_limit": how many of them (1..NXS_PREFIX_MAX, default 8) */
+	bool		wildcardmatch;	/* "wildcardmatch": a free-form leaf with a `*` or `?` stands for its best matching terms */
+	unsigned	wildcard_terms;	/* "wildcard_terms": how many of them (1..NXS_PREFIX_MAX, default 8) */
 	bool		explain;	/* "explain": per result and token the term count and the score contribution */
 } search_params_t;
 

@@ -131,6 +131,11 @@ cfg_from_env(gpu_cfg_t &c)
 		c.complete_host = e && !strcmp(e, "host");
 	}
 	c.explain_rows = u64("NXS_GPU_EXPLAIN_ROWS", 2ull << 20, 1, 1ull << 26);
+	{
+		const char *e = getenv("NXS_GPU_WILDCARD");
+		c.wild_host = e && !strcmp(e, "host");
+	}
+	c.wild_parts = (uint32_t)u64("NXS_GPU_WILD_PARTS", 64, 1, 1024);
 }
 
 /* ------------------------------------------------------------------ */
@@ -658,6 +663,7 @@ nxsgpu_index_destroy(nxsgpu_index_t *ix)
 	(void)hipFree(ix->d_bk);
 	(void)hipFree(ix->d_bk_bytes);
 	sg_free(ix);
+	wc_free(ix);
 	px_free(ix);
 	ex_free(ix);
 	bk_aux_free(ix);

@@ -30,6 +30,8 @@
  *                         suggestions over the same screen (k_sg_dist, k_sg_select)
  *  nxs_gpu_prefix.hip     prefix completion: the live terms in byte order (k_px_keys + radix sort), a
  *                         range per prefix (k_px_range), its k best by df (k_px_select)
+ *  nxs_gpu_wild.hip       wildcard patterns (`*` / `?`) over the same order: the range of the literal head, a scan of
+ *                         it with a running top-k per workgroup (k_wc_match), the parts merged (k_wc_merge)
  *  nxs_gpu_explain.hip    k_explain: per returned doc and query token the term count and the float the
  *                         token added to the score, looked up in the CSR (nxs_explain.h)
  *  nxs_gpu_plan.hip       host only: query classes, the work list (build_worklist) and
@@ -180,6 +182,9 @@ struct gpu_cfg_t {
 	uint32_t	count_mode;	/* NXS_GPU_COUNT=auto|tile|req|scan (COUNT_*): which kernel counts a query's matches */
 	bool		suggest_host;	/* NXS_GPU_SUGGEST=host: every suggestion from the host ranker (nxs_suggest.h): the cross-check */
 	bool		complete_host;	/* NXS_GPU_COMPLETE=host: every completion from the host ranker (nxs_complete.h): the cross-check */
+	bool		wild_host;	/* NXS_GPU_WILDCARD=host: every wildcard pattern from the host ranker (nxs_wild.h): the cross-check */
+	uint32_t	wild_parts;	/* NXS_GPU_WILD_PARTS (64): a pattern's range is cut into at most this many parts, one workgroup
+					 * each (k_wc_match); its partial top-k lists are [parts][k] keys */
 	uint64_t	explain_rows;	/* NXS_GPU_EXPLAIN_ROWS (2 M): (result, token) cells per explain pass -- 17 bytes of workspace a
 					 * cell at most (one-token queries), 36 MB */
 };
@@ -400,6 +405,9 @@ struct nxsgpu_index {
 	 */
 	struct px_state_t *px;
 	uint64_t	px_gen;
+	/* wildcard matching (nxsgpu_wildcard, nxs_gpu_wild.hip) reads that order; its own workspace, staging and
+	 * profile: nothing until the first call */
+	struct wc_state_t *wc;
 	/* explanations (nxsgpu_explain, nxs_gpu_explain.hip): stream, workspace, staging; nothing until the first call */
 	struct ex_state_t *ex;
 };
@@ -629,7 +637,44 @@ int	bk_aux_build(nxsgpu_index_t *ix, const nxsgpu_bknode_t *nodes, uint32_t n);
 void	sg_free(nxsgpu_index_t *ix);		/* everything nxsgpu_suggest has built (index destroy) */
 
 /* ---- nxs_gpu_prefix.hip ---- */
+/*
+ * The live terms in byte order (the header of nxs_gpu_prefix.hip), built by the first call that needs them and
+ * again when nxsgpu_index::px_gen has moved.  Shared by nxsgpu_complete and nxsgpu_wildcard: both passes are
+ * blocking and run on the state's stream, one after the other.
+ */
+struct px_state_t {
+	bool		built;
+	uint64_t	built_gen;
+	uint32_t *	d_node;		/* [n_e] live nodes in byte order of their terms */
+	uint64_t *	d_key;		/* [n_e] ~df << 32 | term id of entry i */
+	uint32_t	n_e;
+	/* the host rankers' dictionary (NXS_GPU_COMPLETE=host, NXS_GPU_WILDCARD=host only): every node with df > 0 */
+	bool		h_built;
+	uint64_t	h_gen;
+	std::vector<nxsgpu_bknode_t> h_nodes;
+	std::vector<uint8_t> h_bytes;
+	std::vector<const uint8_t *> h_terms;
+	std::vector<uint32_t> h_lens, h_dfs, h_ids;
+	hipStream_t	st;
+	void *		ws;
+	size_t		ws_len;
+	uint8_t *	pin;
+	size_t		pin_len;
+	hipEvent_t	ev[3];
+	bool		ev_ok;
+	double		prof[NXSGPU_COMPLETE_PROF];
+	uint64_t	builds;		/* of the order or the host copy, since the index was created */
+};
+/* the state, and the order (host: the host copy instead) of the index's current generation.  0 / -1 */
+int	px_prepare(nxsgpu_index_t *ix, bool host);
+/* k_px_range on `st`: range[i] = the entries of the order that begin with bytes [off[i], off[i + 1]) (all of
+ * them for an empty string), matches[i] (may be NULL) its length; device pointers */
+void	px_launch_range(nxsgpu_index_t *ix, hipStream_t st, const uint8_t *d_bytes, const uint32_t *d_off, uint32_t n,
+	    uint2 *d_range, uint32_t *d_matches);
 void	px_free(nxsgpu_index_t *ix);		/* everything nxsgpu_complete has built (index destroy) */
+
+/* ---- nxs_gpu_wild.hip ---- */
+void	wc_free(nxsgpu_index_t *ix);		/* everything nxsgpu_wildcard has built (index destroy, before px_free) */
 
 /* ---- nxs_gpu_explain.hip ---- */
 void	ex_free(nxsgpu_index_t *ix);		/* everything nxsgpu_explain has built (index destroy) */

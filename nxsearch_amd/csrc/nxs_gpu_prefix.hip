@@ -34,29 +34,6 @@
 
 #define	PX_GROUP	256
 
-struct px_state_t {
-	bool		built;
-	uint64_t	built_gen;
-	uint32_t *	d_node;		/* [n_e] live nodes in byte order of their terms */
-	uint64_t *	d_key;		/* [n_e] ~df << 32 | term id of entry i */
-	uint32_t	n_e;
-	/* the host ranker's dictionary (NXS_GPU_COMPLETE=host only): every node with df > 0 */
-	bool		h_built;
-	uint64_t	h_gen;
-	std::vector<nxsgpu_bknode_t> h_nodes;
-	std::vector<uint8_t> h_bytes;
-	std::vector<const uint8_t *> h_terms;
-	std::vector<uint32_t> h_lens, h_dfs, h_ids;
-	hipStream_t	st;
-	void *		ws;
-	size_t		ws_len;
-	uint8_t *	pin;
-	size_t		pin_len;
-	hipEvent_t	ev[3];
-	bool		ev_ok;
-	double		prof[NXSGPU_COMPLETE_PROF];
-};
-
 static __device__ __forceinline__ uint32_t
 px_df(const uint64_t *__restrict__ post_off, uint32_t n_terms, uint32_t term)
 {
@@ -164,7 +141,19 @@ k_px_range(const nxsgpu_bknode_t *__restrict__ bk, const uint8_t *__restrict__ b
 		}
 	}
 	range[i] = make_uint2(lo, a);
-	matches[i] = a - lo;
+	if (matches) {
+		matches[i] = a - lo;
+	}
+}
+
+void
+px_launch_range(nxsgpu_index_t *ix, hipStream_t st, const uint8_t *d_bytes, const uint32_t *d_off, uint32_t n,
+    uint2 *d_range, uint32_t *d_matches)
+{
+	const px_state_t *px = ix->px;
+
+	hipLaunchKernelGGL(k_px_range, dim3((n + 63) / 64), dim3(64), 0, st,
+	    ix->d_bk, ix->d_bk_bytes, px->d_node, px->n_e, d_bytes, d_off, n, d_range, d_matches);
 }
 
 /*
@@ -331,6 +320,7 @@ px_build_order(nxsgpu_index_t *ix)
 	px->prof[4] = px_now_ms() - t0;
 	px->prof[5] = n_e;
 	px->prof[7] += 1;
+	px->builds++;
 	ret = 0;
 fail:
 	if (ret != 0) {
@@ -391,12 +381,13 @@ px_build_host(nxsgpu_index_t *ix)
 	px->prof[4] = px_now_ms() - t0;
 	px->prof[5] = (double)px->h_terms.size();
 	px->prof[7] += 1;
+	px->builds++;
 	return 0;
 }
 
-/* the state, and the order (or the host copy) of the index's current generation */
-static int
-px_prepare(nxsgpu_index_t *ix)
+/* the state, and the order (host: the host copy) of the index's current generation */
+int
+px_prepare(nxsgpu_index_t *ix, bool host)
 {
 	px_state_t *px = ix->px;
 
@@ -420,7 +411,7 @@ px_prepare(nxsgpu_index_t *ix)
 		}
 		px->ev_ok = true;
 	}
-	if (ix->cfg.complete_host) {
+	if (host) {
 		return px->h_built && px->h_gen == ix->px_gen ? 0 : px_build_host(ix);
 	}
 	return px->built && px->built_gen == ix->px_gen ? 0 : px_build_order(ix);
@@ -486,8 +477,7 @@ px_pass(nxsgpu_index_t *ix, const uint8_t *bytes, const uint32_t *off, uint32_t 
 		return -1;
 	}
 	if (prof) (void)hipEventRecord(px->ev[0], st);
-	hipLaunchKernelGGL(k_px_range, dim3((n + 63) / 64), dim3(64), 0, st,
-	    ix->d_bk, ix->d_bk_bytes, px->d_node, px->n_e, d_bytes, d_off, n, d_range, d_matches);
+	px_launch_range(ix, st, d_bytes, d_off, n, d_range, d_matches);
 	if (prof) (void)hipEventRecord(px->ev[1], st);
 	hipLaunchKernelGGL(k_px_select, dim3(n), dim3(PX_GROUP), 0, st, px->d_key, d_range, k, d_ids, d_df, d_counts);
 	if (prof) (void)hipEventRecord(px->ev[2], st);
@@ -538,7 +528,7 @@ nxsgpu_complete(nxsgpu_index_t *ix, const uint8_t *bytes, const uint32_t *off, u
 		set_error("hipSetDevice failed");
 		return -1;
 	}
-	if (px_prepare(ix) != 0) {
+	if (px_prepare(ix, ix->cfg.complete_host) != 0) {
 		return -1;
 	}
 	px_state_t *px = ix->px;

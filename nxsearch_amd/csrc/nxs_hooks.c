@@ -12,6 +12,7 @@
 #include "nxs_hooks.h"
 #include "nxs_suggest.h"
 #include "nxs_complete.h"
+#include "nxs_wild.h"
 #include "nxs_explain.h"
 
 char *
@@ -276,6 +277,118 @@ nxs_test_prefix_query(const char *query, const char *const *words, const uint32_
 			}
 			nxs_complete_rank(terms, lens, dfs, NULL, n_words, (const uint8_t *)px->val, px->len,
 			    prefix_limit, px->ids, df, &cnt, &m);
+			px->n = cnt;
+			for (uint32_t e = 0; e < cnt; e++) {
+				px->tval[e] = terms[px->ids[e] - 1];
+				px->tlen[e] = (uint16_t)lens[px->ids[e] - 1];
+			}
+		}
+		if (nxs_query_splice(&q) == 0) {
+			repr = nxs_query_repr(&q.parse);
+		}
+	}
+	nxs_query_release(&q);
+	free(terms);
+	free(lens);
+	return repr;
+}
+
+/* the wildcard matcher alone (nxs_wild.h) */
+int
+nxs_test_wild_match(const uint8_t *term, size_t tlen, const uint8_t *pat, size_t plen)
+{
+	return nxs_wild_match(term, tlen, pat, plen);
+}
+
+/* ... as the device runs it: the first 8 bytes from a node's inline copy (zero padded), the rest from the pool */
+int
+nxs_test_wild_match_inl(const uint8_t *term, size_t tlen, const uint8_t *pat, size_t plen)
+{
+	uint8_t inl8[NXS_WILD_INL] = { 0 };
+	uint64_t inl;
+
+	memcpy(inl8, term, tlen < NXS_WILD_INL ? tlen : NXS_WILD_INL);
+	memcpy(&inl, inl8, 8);
+	return nxs_wild_match_inl(inl, NXS_WILD_INL, term, (uint32_t)tlen, pat, (uint32_t)plen);
+}
+
+/*
+ * A pattern of `len` bytes (a NUL is a byte like any other) as nxs_index_wildcard normalises it
+ * (nxs_wild_normalize) -> its result; on 1 the normalised bytes in out (at most cap), *out_len, *literals.
+ */
+int
+nxs_test_wild_normalize(bool lowercase, const char *pat, size_t len, char *out, size_t cap, size_t *out_len,
+    size_t *literals)
+{
+	nxs_index_t fake = { .lowercase = lowercase };
+	char *val = NULL;
+	const int r = nxs_wild_normalize(&fake, pat, len, &val, out_len, literals);
+
+	if (r == 1) {
+		memcpy(out, val, *out_len < cap ? *out_len : cap);
+		free(val);
+	}
+	return r;
+}
+
+/* the host ranker of wildcard matches (nxs_wild.h) over a dictionary handed in: term i has id i + 1 */
+void
+nxs_test_wild_host(const uint8_t *const *terms, const uint32_t *lens, const uint32_t *dfs, uint32_t n_terms,
+    const uint8_t *pat, size_t len, uint32_t k, uint32_t *out_ids, uint32_t *out_df, uint32_t *count,
+    uint32_t *matches)
+{
+	nxs_wild_rank(terms, lens, dfs, NULL, n_terms, pat, len, k, out_ids, out_df, count, matches);
+}
+
+/*
+ * A query with prefix and wildcard leaves against a dictionary handed in (words[i]: term id i + 1, df
+ * dfs[i]): prepare (both flags as given), resolve every leaf with its host ranker, splice.  -> the IR dump
+ * of the result (nxs_query_repr; NULL on error, *errcode = the query's), *n_leaves = the leaves read as
+ * prefixes or patterns, `leaves` = one line per leaf in source order: `p` (prefix) or `w` (wildcard), a
+ * blank and the normalised bytes.
+ */
+char *
+nxs_test_wild_query(const char *query, const char *const *words, const uint32_t *dfs, uint32_t n_words,
+    bool lowercase, bool prefixmatch, bool wildcardmatch, uint32_t prefix_limit, uint32_t wildcard_terms,
+    uint32_t *n_leaves, char *leaves, size_t cap, int *errcode)
+{
+	nxs_index_t fake = { .lowercase = lowercase };
+	const uint8_t **terms = calloc(n_words + 1, sizeof(*terms));
+	uint32_t *lens = calloc(n_words + 1, sizeof(*lens));
+	char *repr = NULL;
+	size_t o = 0;
+	qprep_t q;
+
+	nxs_query_prepare_wc(&fake, query, prefixmatch, wildcardmatch, &q);
+	*n_leaves = (uint32_t)q.n_pfx;
+	*errcode = (int)q.errcode;
+	if (leaves && cap) {
+		leaves[0] = '\0';
+	}
+	for (uint32_t w = 0; terms && lens && w < n_words; w++) {
+		terms[w] = (const uint8_t *)words[w];
+		lens[w] = (uint32_t)strlen(words[w]);
+	}
+	if (!q.errcode && terms && lens) {
+		for (size_t i = q.n_pfx; i-- > 0; ) {
+			qpfx_t *px = &q.pfx[i];
+			uint32_t df[NXS_PREFIX_MAX], cnt = 0, m = 0;
+
+			if (leaves && o + px->len + 4 <= cap) {
+				leaves[o++] = px->kind == QPFX_WILD ? 'w' : 'p';
+				leaves[o++] = ' ';
+				memcpy(leaves + o, px->val, px->len);
+				o += px->len;
+				leaves[o++] = '\n';
+				leaves[o] = '\0';
+			}
+			if (px->kind == QPFX_WILD) {
+				nxs_wild_rank(terms, lens, dfs, NULL, n_words, (const uint8_t *)px->val, px->len,
+				    wildcard_terms, px->ids, df, &cnt, &m);
+			} else {
+				nxs_complete_rank(terms, lens, dfs, NULL, n_words, (const uint8_t *)px->val, px->len,
+				    prefix_limit, px->ids, df, &cnt, &m);
+			}
 			px->n = cnt;
 			for (uint32_t e = 0; e < cnt; e++) {
 				px->tval[e] = terms[px->ids[e] - 1];

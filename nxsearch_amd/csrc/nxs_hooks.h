@@ -99,6 +99,26 @@ char *		nxs_test_prefix_query(const char *query, const char *const *words, const
 		    char *prefixes, size_t cap);
 char *		nxs_test_filter_prefix(const char *basedir, int stages, const char *s, int *act);
 
+/* wildcard matching: the matcher alone (nxs_wild.h; _inl: as the device runs it, the first 8 bytes from an inline
+ * copy), the host ranker over a dictionary handed in (term i has id i + 1), the parameters as
+ * nxs_index_wildcard and a search read them, a wildcard object built by hand, and a query's prefix and
+ * wildcard leaves marked, resolved with the host rankers and spliced (-> nxs_query_repr of the result;
+ * `leaves`: a line `p <prefix>` or `w <pattern>` per leaf, source order) */
+int		nxs_test_wild_match(const uint8_t *term, size_t tlen, const uint8_t *pat, size_t plen);
+int		nxs_test_wild_match_inl(const uint8_t *term, size_t tlen, const uint8_t *pat, size_t plen);
+void		nxs_test_wild_host(const uint8_t *const *terms, const uint32_t *lens, const uint32_t *dfs,
+		    uint32_t n_terms, const uint8_t *pat, size_t len, uint32_t k,
+		    uint32_t *out_ids, uint32_t *out_df, uint32_t *count, uint32_t *matches);
+int		nxs_test_wild_params(nxs_t *, nxs_params_t *, unsigned *k, int *wildcardmatch, unsigned *wildcard_terms);
+/* ... a pattern of `len` bytes as the call normalises it (nxs_wild_normalize's result; out: at most cap bytes) */
+int		nxs_test_wild_normalize(bool lowercase, const char *pat, size_t len, char *out, size_t cap,
+		    size_t *out_len, size_t *literals);
+nxs_sugg_t *	nxs_test_wild_build(const char *pattern, size_t pattern_len, uint64_t matches, unsigned count,
+		    const uint8_t *const *terms, const size_t *lens, const uint64_t *dfs);
+char *		nxs_test_wild_query(const char *query, const char *const *words, const uint32_t *dfs,
+		    uint32_t n_words, bool lowercase, bool prefixmatch, bool wildcardmatch, uint32_t prefix_limit,
+		    uint32_t wildcard_terms, uint32_t *n_leaves, char *leaves, size_t cap, int *errcode);
+
 /* explanations: the "explain" key as a search reads it, a response built by hand from given arrays (accessors
  * and the JSON writer without an index; cells [count][n_tok], tf == 0 = absent), and the searches of the shared
  * header nxs_explain.h over a list handed in (pos: nxs_ex_find, UINT64_MAX = absent; lower: nxs_ex_lower;

@@ -281,9 +281,16 @@ typedef struct {
  * been resolved (nxsgpu_complete) -- its expansions: the first min(prefix_limit, matches) eligible terms in
  * the order df descending, term id ascending.  nxs_query_splice puts them in the leaf's place.
  */
-#define	NXS_PREFIX_MAX		32	/* "prefix_limit" at most */
+#define	NXS_PREFIX_MAX		32	/* "prefix_limit" / "wildcard_terms" at most */
+/*
+ * A wildcard leaf (a `*` or `?` and at least one other byte, under "wildcardmatch") is recorded the same way:
+ * `val` is the normalised pattern (nxs_wild_normalize), the expansions come from nxsgpu_wildcard and number
+ * min(wildcard_terms, matches).
+ */
+enum { QPFX_PREFIX = 0, QPFX_WILD = 1 };
 typedef struct {
 	size_t		item;		/* the leaf: index into parse.items */
+	int		kind;		/* QPFX_* */
 	char *		val;		/* malloc'd, NUL-terminated */
 	size_t		len;
 	uint32_t	n;		/* expansions */
@@ -316,6 +323,20 @@ void	nxs_query_prepare(const nxs_index_t *, const char *query, qprep_t *out);
 /* the same; prefixmatch: a leaf from a free-form string that ends in `*` (and is longer) is a prefix leaf --
  * kept out of the token list, recorded in out->pfx */
 void	nxs_query_prepare_px(const nxs_index_t *, const char *query, bool prefixmatch, qprep_t *out);
+/* the same with both flags; wildcardmatch: a leaf from a free-form string that holds a `*` or `?` and at least
+ * one other byte is a wildcard leaf -- unless prefixmatch is set too and it is a literal followed by a single
+ * trailing `*`, which stays the prefix leaf it is.  A pattern that normalises to more than NXS_WILD_MAXLEN
+ * bytes fails its query (NXS_ERR_INVALID "wildcard pattern too long") */
+void	nxs_query_prepare_wc(const nxs_index_t *, const char *query, bool prefixmatch, bool wildcardmatch, qprep_t *out);
+/*
+ * A wildcard pattern as the matcher takes it: cut at its metacharacters, every literal piece through the
+ * normalizer / lowercase stage only (the rule of a prefix: a fragment is not a word), put back together, runs
+ * of `*` collapsed to one.  idx NULL: no filters.  1 = *out (malloc'd, NUL-terminated) / *out_len; 0 = no
+ * literal byte is left (not served); -1 = the filters failed, -2 = out of memory, -3 = longer than
+ * NXS_WILD_MAXLEN.  *literals (may be NULL) = its bytes that are no metacharacter.
+ */
+int	nxs_wild_normalize(const nxs_index_t *, const char *str, size_t len, char **out, size_t *out_len, size_t *literals)
+	    __attribute__((visibility("hidden")));
 /* every prefix leaf becomes (e1 OR e2 OR ... OR em), the token list what the rewritten query's would be;
  * m = 0: the leaf stays the empty set.  0 / -1 (out of memory) */
 int	nxs_query_splice(qprep_t *);

@@ -1,7 +1,7 @@
 /*
  * nxs_lookup.c -- dictionary lookups by string: spelling suggestions
- * (nxs_index_suggest) and prefix completions (nxs_index_complete), and the
- * object both return (nxs_sugg_t).
+ * (nxs_index_suggest), prefix completions (nxs_index_complete) and wildcard
+ * matches (nxs_index_wildcard), and the object all three return (nxs_sugg_t).
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -10,8 +10,9 @@
 #include "nxs_api_int.h"
 #include "nxs_hooks.h"
 #include "nxs_suggest.h"
+#include "nxs_wild.h"
 
-/* ---- the object of both calls (nxs_sugg_t) --------------------------------------------- */
+/* ---- the object of the calls (nxs_sugg_t)  --------------------------------------------- */
 
 typedef struct {
 	char *		term;		/* owned by the object, NUL-terminated */
@@ -24,11 +25,14 @@ struct nxs_sugg {
 	char *		token;		/* the token after the filters (empty when dropped) */
 	size_t		token_len;
 	bool		dropped;
-	bool		completion;	/* built by nxs_index_complete: `token` is the prefix, the JSON has its own shape */
+	int		kind;		/* SUGG_*: by nxs_index_complete / _wildcard `token` is the prefix / the pattern, the
+					 * JSON has its own shape */
 	uint64_t	matches;
 	unsigned	count;
 	sugg_item_t	items[];
 };
+
+enum { SUGG_SUGGEST = 0, SUGG_COMPLETE = 1, SUGG_WILD = 2 };
 
 /* one block: the object, its items, the strings */
 static nxs_sugg_t *
@@ -52,7 +56,7 @@ sugg_build(const char *token, size_t token_len, bool dropped, uint64_t matches, 
 	str[token_len] = '\0';
 	str += token_len + 1;
 	sg->dropped = dropped;
-	sg->completion = false;
+	sg->kind = SUGG_SUGGEST;
 	sg->matches = matches;
 	sg->count = count;
 	for (unsigned i = 0; i < count; i++) {
@@ -105,10 +109,13 @@ nxs_sugg_release(nxs_sugg_t *sg)
 }
 
 /* {"token":"...","suggestions":[{"term":"...","distance":D,"df":N},...],"matches":M}; of a completion:
- * {"prefix":"...","completions":[{"term":"...","df":N},...],"matches":M} */
+ * {"prefix":"...","completions":[{"term":"...","df":N},...],"matches":M}; of a wildcard match:
+ * {"pattern":"...","terms":[{"term":"...","df":N},...],"matches":M} */
 char *
 nxs_sugg_tojson(nxs_sugg_t *sg, size_t *len)
 {
+	static const char *const head[] = { "{\"token\":", "{\"prefix\":", "{\"pattern\":" };
+	static const char *const list[] = { ",\"suggestions\":[", ",\"completions\":[", ",\"terms\":[" };
 	size_t cap = 96 + 6 * sg->token_len, o = 0;
 	char *s;
 
@@ -118,13 +125,13 @@ nxs_sugg_tojson(nxs_sugg_t *sg, size_t *len)
 	if ((s = malloc(cap)) == NULL) {
 		return NULL;
 	}
-	o += (size_t)sprintf(s + o, sg->completion ? "{\"prefix\":" : "{\"token\":");
+	o += (size_t)sprintf(s + o, "%s", head[sg->kind]);
 	o += json_str(s + o, sg->token, sg->token_len);
-	o += (size_t)sprintf(s + o, sg->completion ? ",\"completions\":[" : ",\"suggestions\":[");
+	o += (size_t)sprintf(s + o, "%s", list[sg->kind]);
 	for (unsigned i = 0; i < sg->count; i++) {
 		o += (size_t)sprintf(s + o, "%s{\"term\":", i ? "," : "");
 		o += json_str(s + o, sg->items[i].term, sg->items[i].len);
-		if (sg->completion) {
+		if (sg->kind != SUGG_SUGGEST) {
 			o += (size_t)sprintf(s + o, ",\"df\":%llu}", (unsigned long long)sg->items[i].df);
 		} else {
 			o += (size_t)sprintf(s + o, ",\"distance\":%u,\"df\":%llu}", sg->items[i].dist,
@@ -138,7 +145,7 @@ nxs_sugg_tojson(nxs_sugg_t *sg, size_t *len)
 	return s;
 }
 
-/* ---- the path both calls take: enter, stage, pack, (the device call), build ------------------------- */
+/* ---- the path the calls take: enter, stage, pack, (the device call), build ------------------------- */
 
 /* the strings of one call: what the filters made of them, the kept ones packed for the device, its answers */
 typedef struct {
@@ -276,11 +283,12 @@ lookup_pack(nxs_t *nxs, lookup_t *st, unsigned k)
 /*
  * String i's object from the device's answer to packed string *nd (stepped here), or its failure: NULL with
  * errs[i] and the error set.  `noun` names the string in messages.  dist == NULL: the device sends no
- * distances -- the terms start with the string, and the pair's true Levenshtein distance is what they add.
+ * distances -- every term holds the string's `lit` literal bytes (a prefix: all of it, and the pair's true
+ * Levenshtein distance is what the term adds), and the distance reported is what it holds beyond them.
  */
 static nxs_sugg_t *
 lookup_build(nxs_index_t *idx, const lookup_t *st, size_t i, size_t *nd, unsigned k, const uint8_t *dist,
-    const char *noun, nxs_err_t *errs)
+    size_t lit, const char *noun, nxs_err_t *errs)
 {
 	const uint8_t *terms[NXS_SUGGEST_MAX];
 	size_t tlens[NXS_SUGGEST_MAX];
@@ -302,13 +310,13 @@ lookup_build(nxs_index_t *idx, const lookup_t *st, size_t i, size_t *nd, unsigne
 	for (unsigned j = 0; j < c; j++) {
 		const uint32_t id = st->ids[at * k + j];
 
-		if (id < 1 || id > idx->last_id || (!dist && idx->terms[id].len < st->s[i].len)) {
+		if (id < 1 || id > idx->last_id || (!dist && idx->terms[id].len < lit)) {
 			nxs_decl_err(idx->nxs, code, "the device named an unknown term for %s %zu", noun, i);
 			goto fail;
 		}
 		terms[j] = idx->terms[id].val;
 		tlens[j] = idx->terms[id].len;
-		dists[j] = dist ? dist[at * k + j] : (unsigned)(tlens[j] - st->s[i].len);
+		dists[j] = dist ? dist[at * k + j] : (unsigned)(tlens[j] - lit);
 		dfs[j] = st->df[at * k + j];
 	}
 	if ((sg = sugg_build(st->s[i].val, st->s[i].len, false, st->matches[at], c, terms, tlens, dists, dfs)) != NULL) {
@@ -389,7 +397,7 @@ suggest_run(nxs_index_t *idx, nxs_params_t *params, const char *const *tokens, c
 	}
 	for (size_t i = 0; i < n; i++) {
 		if (st.s[i].act != 0) {
-			out[i] = lookup_build(idx, &st, i, &nd, k, st.dist, "token", errs);
+			out[i] = lookup_build(idx, &st, i, &nd, k, st.dist, 0, "token", errs);
 		} else if ((out[i] = sugg_build("", 0, true, 0, 0, NULL, NULL, NULL, NULL)) == NULL) {
 			/* (the filters dropped the token: an object that says so) */
 			if (errs) {
@@ -459,7 +467,7 @@ complete_run(nxs_index_t *idx, nxs_params_t *params, const char *const *prefixes
 	}
 	for (size_t i = 0; i < n; i++) {
 		if (st.s[i].act != 0) {
-			out[i] = lookup_build(idx, &st, i, &nd, k, NULL, "prefix", errs);
+			out[i] = lookup_build(idx, &st, i, &nd, k, NULL, st.s[i].len, "prefix", errs);
 		} else {
 			if (errs) {
 				errs[i] = NXS_ERR_INVALID;
@@ -467,7 +475,7 @@ complete_run(nxs_index_t *idx, nxs_params_t *params, const char *const *prefixes
 			nxs_decl_err(nxs, NXS_ERR_INVALID, "empty prefix");
 		}
 		if (out[i]) {
-			out[i]->completion = true;
+			out[i]->kind = SUGG_COMPLETE;
 		}
 		failed += !out[i];
 	}
@@ -492,6 +500,125 @@ nxs_index_complete(nxs_index_t *idx, nxs_params_t *params, const char *prefix, s
 	(void)complete_run(idx, params, &prefix, &len, 1, &sg, NULL);	/* (as nxs_index_suggest) */
 	return sg;
 }
+
+/* ---- wildcard matching (nxs_index_wildcard) -------------------------------------------- */
+
+/* lens: NULL = the strings are NUL-terminated */
+static int
+wildcard_run(nxs_index_t *idx, nxs_params_t *params, const char *const *patterns, const size_t *lens, size_t n,
+    nxs_sugg_t **out, nxs_err_t *errs)
+{
+	nxs_t *nxs = idx->nxs;
+	lookup_t st = { 0 };
+	size_t *lit = NULL;
+	unsigned k;
+	size_t nd = 0;
+	int ret = -1, failed = 0;
+
+	nxs_clear_error(nxs);
+	outs_clear(out, errs, n);
+	if (get_limit_param(nxs, params, "wildcard_limit", &k) == -1 || lookup_enter(idx, "wildcard", n) == -1) {
+		return -1;
+	}
+	/* every literal piece through the normalizer / lowercase stage only, runs of stars collapsed
+	 * (nxs_wild_normalize).  act: 1 = goes to the device, 0 = no literal byte, -1 = the filters failed,
+	 * -3 = too long (-2: out of memory fails the call) */
+	st.n = n;
+	st.s = calloc(n ? n : 1, sizeof(*st.s));
+	lit = calloc(n ? n : 1, sizeof(*lit));
+	if (!st.s || !lit) {
+		nxs_decl_err(nxs, NXS_ERR_SYSTEM, "out of memory");
+		goto out;
+	}
+	for (size_t i = 0; i < n; i++) {
+		st.s[i].act = nxs_wild_normalize(idx, patterns[i], lens ? lens[i] : strlen(patterns[i]), &st.s[i].val,
+		    &st.s[i].len, &lit[i]);
+		if (st.s[i].act == -2) {
+			nxs_decl_err(nxs, NXS_ERR_SYSTEM, "out of memory");
+			goto out;
+		}
+	}
+	if (lookup_pack(nxs, &st, k) == -1) {
+		goto out;
+	}
+	if (st.nd && nxsgpu_wildcard(idx->dev, st.bytes, st.off, (uint32_t)st.nd, k, st.ids, st.df, st.counts,
+	    st.matches) != 0) {
+		nxs_decl_err(nxs, NXS_ERR_FATAL, "device wildcard pass failed: %s", nxsgpu_last_error());
+		goto out;
+	}
+	for (size_t i = 0; i < n; i++) {
+		if (st.s[i].act == 1 || st.s[i].act == -1) {
+			out[i] = lookup_build(idx, &st, i, &nd, k, NULL, lit[i], "pattern", errs);
+		} else {
+			if (errs) {
+				errs[i] = NXS_ERR_INVALID;
+			}
+			nxs_decl_err(nxs, NXS_ERR_INVALID, st.s[i].act == 0 ? "empty pattern" : "wildcard pattern too long");
+		}
+		if (out[i]) {
+			out[i]->kind = SUGG_WILD;
+		}
+		failed += !out[i];
+	}
+	ret = failed;
+out:
+	free(lit);
+	lookup_free(&st);
+	return ret;
+}
+
+int
+nxs_index_wildcard_batch(nxs_index_t *idx, nxs_params_t *params, const char *const *patterns, size_t n,
+    nxs_sugg_t **out, nxs_err_t *errs)
+{
+	return wildcard_run(idx, params, patterns, NULL, n, out, errs);
+}
+
+nxs_sugg_t *
+nxs_index_wildcard(nxs_index_t *idx, nxs_params_t *params, const char *pattern, size_t len)
+{
+	nxs_sugg_t *sg = NULL;
+
+	(void)wildcard_run(idx, params, &pattern, &len, 1, &sg, NULL);	/* (as nxs_index_suggest) */
+	return sg;
+}
+
+#ifdef NXS_TEST_HOOKS
+/* the parameters as nxs_index_wildcard / a search read them: 0, or -1 with the error declared */
+int
+nxs_test_wild_params(nxs_t *nxs, nxs_params_t *params, unsigned *k, int *wildcardmatch, unsigned *wildcard_terms)
+{
+	nxs_index_t fake = { .nxs = nxs };
+	search_params_t sp;
+
+	nxs_clear_error(nxs);
+	if (get_limit_param(nxs, params, "wildcard_limit", k) == -1 || get_search_params(&fake, params, &sp) == -1) {
+		return -1;
+	}
+	*wildcardmatch = sp.wildcardmatch;
+	*wildcard_terms = sp.wildcard_terms;
+	return 0;
+}
+
+/* an nxs_sugg_t of the wildcard kind built by hand: distance = len(term) - the pattern's literal bytes */
+nxs_sugg_t *
+nxs_test_wild_build(const char *pattern, size_t pattern_len, uint64_t matches, unsigned count,
+    const uint8_t *const *terms, const size_t *lens, const uint64_t *dfs)
+{
+	unsigned dists[NXS_SUGGEST_MAX];
+	uint32_t lit, minlen;
+	nxs_sugg_t *sg;
+
+	(void)nxs_wild_shape((const uint8_t *)pattern, (uint32_t)pattern_len, &lit, &minlen);
+	for (unsigned i = 0; i < count && i < NXS_SUGGEST_MAX; i++) {
+		dists[i] = (unsigned)(lens[i] - lit);
+	}
+	if ((sg = sugg_build(pattern, pattern_len, false, matches, count, terms, lens, dists, dfs)) != NULL) {
+		sg->kind = SUGG_WILD;
+	}
+	return sg;
+}
+#endif /* NXS_TEST_HOOKS */
 
 #ifdef NXS_TEST_HOOKS
 /* the parameters as nxs_index_complete / a search read them: 0, or -1 with the error declared */
@@ -522,7 +649,7 @@ nxs_test_compl_build(const char *prefix, size_t prefix_len, uint64_t matches, un
 		dists[i] = (unsigned)(lens[i] - prefix_len);
 	}
 	if ((sg = sugg_build(prefix, prefix_len, false, matches, count, terms, lens, dists, dfs)) != NULL) {
-		sg->completion = true;
+		sg->kind = SUGG_COMPLETE;
 	}
 	return sg;
 }

@@ -547,6 +547,8 @@ get_search_params(nxs_index_t *idx, nxs_params_t *params, search_params_t *sp)
 	sp->total = false;
 	sp->prefixmatch = false;
 	sp->prefix_limit = 8;
+	sp->wildcardmatch = false;
+	sp->wildcard_terms = 8;
 	sp->explain = false;
 	sp->algo = idx->algo;
 	if (!params) {
@@ -580,6 +582,16 @@ get_search_params(nxs_index_t *idx, nxs_params_t *params, search_params_t *sp)
 			return -1;
 		}
 		sp->prefix_limit = (unsigned)v;
+	}
+	if (nxs_params_get_bool(params, "wildcardmatch", &fl) == 0 && fl) {
+		sp->wildcardmatch = true;
+	}
+	if (nxs_params_get_uint(params, "wildcard_terms", &v) == 0) {
+		if (v < 1 || v > NXS_PREFIX_MAX) {
+			nxs_decl_err(idx->nxs, NXS_ERR_INVALID, "invalid wildcard_terms (1..%d)", NXS_PREFIX_MAX);
+			return -1;
+		}
+		sp->wildcard_terms = (unsigned)v;
 	}
 	return 0;
 }

@@ -22,6 +22,7 @@
  * nxsgpu_query_t and queries without errors are kept.  NXS_PLAN_CACHE=0 turns it off.
  * Under "prefixmatch" a string that holds a `*` bypasses the cache: what a prefix leaf stands for depends
  * on prefix_limit and on the df of the moment, and the same string means something else with the flag off.
+ * The same holds for a string with a `*` or `?` under "wildcardmatch".
  */
 typedef struct {
 	uint64_t	h;
@@ -185,7 +186,8 @@ plan_parse_chunk(void *arg, size_t lo, size_t hi)
 	for (size_t i = lo; i < hi; i++) {
 		qprep_t *q = &j->prep[i];
 
-		if (j->pc && !(j->sp->prefixmatch && strchr(j->queries[i], '*'))) {
+		if (j->pc && !(j->sp->prefixmatch && strchr(j->queries[i], '*')) &&
+		    !(j->sp->wildcardmatch && strpbrk(j->queries[i], "*?"))) {
 			const pc_ent_t *e = plan_cache_find(j->pc, j->queries[i], strlen(j->queries[i]), j->sp->fuzzymatch);
 			if (e) {
 				memset(q, 0, sizeof(*q));
@@ -195,7 +197,7 @@ plan_parse_chunk(void *arg, size_t lo, size_t hi)
 				continue;
 			}
 		}
-		nxs_query_prepare_px(j->idx, j->queries[i], j->sp->prefixmatch, q);
+		nxs_query_prepare_wc(j->idx, j->queries[i], j->sp->prefixmatch, j->sp->wildcardmatch, q);
 		if (q->errcode) {
 			nxs_query_release_scratch(q);	/* (what the second pass would do for it) */
 			q->compiled = true;
@@ -262,16 +264,17 @@ pfx_ref_cmp(const void *a, const void *b)
 }
 
 /*
- * The prefix leaves of a batch: its distinct prefixes are resolved by ONE blocking completion pass
- * (nxsgpu_complete, k = prefix_limit), each leaf's expansions are spliced into its query's program and token
- * list (nxs_query_splice), and a query that waits for nothing else is compiled.  A batch without a prefix
- * leaf makes no call.
+ * The prefix and wildcard leaves of a batch.  Per kind, the batch's distinct strings are resolved by ONE
+ * blocking device pass -- nxsgpu_complete with k = prefix_limit, nxsgpu_wildcard with k = wildcard_terms
+ * (plan_resolve) -- then each leaf's expansions are spliced into its query's program and token list
+ * (nxs_query_splice), and a query that waits for nothing else is compiled.  A batch without such a leaf
+ * makes no call.
  */
 static int
-plan_prefixes(nxs_index_t *idx, const search_params_t *sp, size_t n, qprep_t *prep)
+plan_resolve(nxs_index_t *idx, size_t n, qprep_t *prep, int kind, unsigned k)
 {
 	nxs_t *nxs = idx->nxs;
-	const unsigned k = sp->prefix_limit;
+	const char *what = kind == QPFX_WILD ? "wildcard" : "complete";
 	size_t n_ref = 0, nd = 0, blen = 0, r = 0;
 	pfx_ref_t *ref = NULL;
 	uint8_t *bytes = NULL;
@@ -279,14 +282,17 @@ plan_prefixes(nxs_index_t *idx, const search_params_t *sp, size_t n, qprep_t *pr
 	int ret = -1;
 
 	for (size_t i = 0; i < n; i++) {
-		n_ref += prep[i].errcode ? 0 : prep[i].n_pfx;
+		for (size_t j = 0; !prep[i].errcode && j < prep[i].n_pfx; j++) {
+			n_ref += prep[i].pfx[j].kind == kind;
+		}
 	}
 	if (!n_ref) {
 		return 0;
 	}
 	/* (a shard's postings are its own: the df the order rests on would be the shard's; include/nxs.h) */
 	if (idx->n_shards) {
-		nxs_decl_err(nxs, NXS_ERR_INVALID, "prefixmatch is not available on a doc shard");
+		nxs_decl_err(nxs, NXS_ERR_INVALID, "%s is not available on a doc shard",
+		    kind == QPFX_WILD ? "wildcardmatch" : "prefixmatch");
 		return -1;
 	}
 	if ((ref = malloc(n_ref * sizeof(*ref))) == NULL) {
@@ -295,7 +301,9 @@ plan_prefixes(nxs_index_t *idx, const search_params_t *sp, size_t n, qprep_t *pr
 	}
 	for (size_t i = 0; i < n; i++) {
 		for (size_t j = 0; !prep[i].errcode && j < prep[i].n_pfx; j++) {
-			ref[r++] = (pfx_ref_t){ prep[i].pfx[j].val, prep[i].pfx[j].len, (uint32_t)i, (uint32_t)j, 0 };
+			if (prep[i].pfx[j].kind == kind) {
+				ref[r++] = (pfx_ref_t){ prep[i].pfx[j].val, prep[i].pfx[j].len, (uint32_t)i, (uint32_t)j, 0 };
+			}
 		}
 	}
 	qsort(ref, n_ref, sizeof(*ref), pfx_ref_cmp);
@@ -333,8 +341,9 @@ plan_prefixes(nxs_index_t *idx, const search_params_t *sp, size_t n, qprep_t *pr
 			goto out;
 		}
 	}
-	if (nxsgpu_complete(idx->dev, bytes, off, (uint32_t)nd, k, ids, df, counts, matches) != 0) {
-		nxs_decl_err(nxs, NXS_ERR_FATAL, "device complete pass failed: %s", nxsgpu_last_error());
+	if ((kind == QPFX_WILD ? nxsgpu_wildcard : nxsgpu_complete)(idx->dev, bytes, off, (uint32_t)nd, k, ids, df,
+	    counts, matches) != 0) {
+		nxs_decl_err(nxs, NXS_ERR_FATAL, "device %s pass failed: %s", what, nxsgpu_last_error());
 		goto out;
 	}
 	for (r = 0; r < n_ref; r++) {
@@ -344,32 +353,13 @@ plan_prefixes(nxs_index_t *idx, const search_params_t *sp, size_t n, qprep_t *pr
 		px->n = counts[ref[r].slot] <= k ? counts[ref[r].slot] : k;
 		for (uint32_t e = 0; e < px->n; e++) {
 			if (row[e] < 1 || row[e] > idx->last_id) {
-				nxs_decl_err(nxs, NXS_ERR_FATAL, "the device named an unknown term for a prefix");
+				nxs_decl_err(nxs, NXS_ERR_FATAL, "the device named an unknown term for a %s",
+				    kind == QPFX_WILD ? "pattern" : "prefix");
 				goto out;
 			}
 			px->ids[e] = row[e];
 			px->tval[e] = idx->terms[row[e]].val;
 			px->tlen[e] = idx->terms[row[e]].len;
-		}
-	}
-	for (size_t i = 0; i < n; i++) {
-		qprep_t *q = &prep[i];
-		bool miss = false;
-
-		if (q->errcode || !q->n_pfx) {
-			continue;
-		}
-		if (nxs_query_splice(q) == -1) {
-			nxs_decl_err(nxs, NXS_ERR_SYSTEM, "out of memory");
-			goto out;
-		}
-		for (size_t j = 0; j < q->n_tokens; j++) {
-			miss = miss || !q->tokens[j].term_id;
-		}
-		if (!miss || !sp->fuzzymatch) {
-			(void)nxs_query_compile(q);
-			nxs_query_release_scratch(q);
-			q->compiled = true;
 		}
 	}
 	ret = 0;
@@ -384,6 +374,36 @@ out:
 	return ret;
 }
 
+static int
+plan_prefixes(nxs_index_t *idx, const search_params_t *sp, size_t n, qprep_t *prep)
+{
+	if (plan_resolve(idx, n, prep, QPFX_PREFIX, sp->prefix_limit) == -1 ||
+	    plan_resolve(idx, n, prep, QPFX_WILD, sp->wildcard_terms) == -1) {
+		return -1;
+	}
+	for (size_t i = 0; i < n; i++) {
+		qprep_t *q = &prep[i];
+		bool miss = false;
+
+		if (q->errcode || !q->n_pfx) {
+			continue;
+		}
+		if (nxs_query_splice(q) == -1) {
+			nxs_decl_err(idx->nxs, NXS_ERR_SYSTEM, "out of memory");
+			return -1;
+		}
+		for (size_t j = 0; j < q->n_tokens; j++) {
+			miss = miss || !q->tokens[j].term_id;
+		}
+		if (!miss || !sp->fuzzymatch) {
+			(void)nxs_query_compile(q);
+			nxs_query_release_scratch(q);
+			q->compiled = true;
+		}
+	}
+	return 0;
+}
+
 /* parse + lookups (+ compile for the queries without misses) on the worker threads; the misses into *fz */
 int
 plan_front(nxs_index_t *idx, const search_params_t *sp, const char *const *queries,
@@ -396,7 +416,7 @@ plan_front(nxs_index_t *idx, const search_params_t *sp, const char *const *queri
 
 	memset(fz, 0, sizeof(*fz));
 	pool_run(pool, plan_parse_chunk, &job, n, 16);
-	if (sp->prefixmatch && plan_prefixes(idx, sp, n, prep) == -1) {
+	if ((sp->prefixmatch || sp->wildcardmatch) && plan_prefixes(idx, sp, n, prep) == -1) {
 		return -1;
 	}
 

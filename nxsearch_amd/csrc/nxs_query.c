@@ -20,6 +20,7 @@
 #include <string.h>
 
 #include "nxs_impl.h"
+#include "nxs_wild.h"
 
 /* ---- lexer -------------------------------------------------------------- */
 
@@ -468,8 +469,130 @@ prepare_prefix(const nxs_index_t *idx, qprep_t *out, size_t item, const char *st
 	return 1;
 }
 
+int
+nxs_wild_normalize(const nxs_index_t *idx, const char *str, size_t len, char **out, size_t *out_len, size_t *literals)
+{
+	char *res = malloc(len + 1);
+	size_t cap = len + 1, o = 0, lit = 0;
+	int ret = -2;
+
+	if (!res) {
+		return -2;
+	}
+	for (size_t i = 0; i < len; ) {
+		size_t j = i, plen;
+		char *piece;
+
+		if (nxs_wild_meta((uint8_t)str[i])) {
+			if (!(str[i] == '*' && o && res[o - 1] == '*')) {
+				res[o++] = str[i];	/* (room: the reserve below) */
+			}
+			i++;
+			continue;
+		}
+		while (j < len && !nxs_wild_meta((uint8_t)str[j])) {
+			j++;
+		}
+		plen = j - i;
+		/* (not strndup: the length is explicit, a piece may hold a NUL) */
+		if ((piece = malloc(plen + 1)) == NULL) {
+			goto out;
+		}
+		memcpy(piece, str + i, plen);
+		piece[plen] = '\0';
+		if (idx && nxs_index_filter(idx, NXS_FSTAGE_NORMALIZER, &piece, &plen) < 0) {
+			free(piece);
+			ret = -1;
+			goto out;
+		}
+		/* a piece may grow under the normalizer: room for it and for every metacharacter still to come */
+		if (o + plen + (len - j) + 1 > cap) {
+			char *nr = realloc(res, o + plen + (len - j) + 1);
+			if (!nr) {
+				free(piece);
+				goto out;
+			}
+			res = nr;
+			cap = o + plen + (len - j) + 1;
+		}
+		memcpy(res + o, piece, plen);
+		o += plen;
+		lit += plen;
+		free(piece);
+		i = j;
+	}
+	if (lit == 0) {
+		ret = 0;
+		goto out;
+	}
+	if (o > NXS_WILD_MAXLEN) {
+		ret = -3;
+		goto out;
+	}
+	res[o] = '\0';
+	*out = res;
+	*out_len = o;
+	if (literals) {
+		*literals = lit;
+	}
+	return 1;
+out:
+	free(res);
+	return ret;
+}
+
+/* A wildcard leaf: 1 = recorded in out->pfx, 0 = no literal byte is left (the leaf is the empty set), -1 =
+ * error (out->errcode set) */
+static int
+prepare_wild(const nxs_index_t *idx, qprep_t *out, size_t item, const char *str, size_t len)
+{
+	char *val = NULL;
+	qpfx_t *px;
+	const int r = nxs_wild_normalize(idx, str, len, &val, &len, NULL);
+
+	if (r == 0) {
+		return 0;
+	}
+	if (r < 0) {
+		out->errcode = r == -3 ? NXS_ERR_INVALID : r == -2 ? NXS_ERR_SYSTEM : NXS_ERR_FATAL;
+		out->errmsg = strdup(r == -3 ? "wildcard pattern too long" : r == -2 ? "out of memory" : "query_prepare() failed");
+		return -1;
+	}
+	px = &out->pfx[out->n_pfx++];
+	memset(px, 0, sizeof(*px));
+	px->item = item;
+	px->kind = QPFX_WILD;
+	px->val = val;
+	px->len = len;
+	return 1;
+}
+
+/* what a free-form leaf is under the two flags: QPFX_PREFIX, QPFX_WILD, or -1: an ordinary leaf */
+static int
+leaf_kind(const char *val, size_t len, bool prefixmatch, bool wildcardmatch)
+{
+	size_t meta = 0;
+
+	for (size_t i = 0; i < len; i++) {
+		meta += nxs_wild_meta((uint8_t)val[i]);
+	}
+	if (prefixmatch && len >= 2 && val[len - 1] == '*' && (meta == 1 || !wildcardmatch)) {
+		return QPFX_PREFIX;	/* (with prefixmatch alone any leaf that ends in a star, as ever) */
+	}
+	if (wildcardmatch && meta && meta < len) {
+		return QPFX_WILD;
+	}
+	return -1;
+}
+
 void
 nxs_query_prepare_px(const nxs_index_t *idx, const char *query, bool prefixmatch, qprep_t *out)
+{
+	nxs_query_prepare_wc(idx, query, prefixmatch, false, out);
+}
+
+void
+nxs_query_prepare_wc(const nxs_index_t *idx, const char *query, bool prefixmatch, bool wildcardmatch, qprep_t *out)
 {
 	qparse_t *pr = &out->parse;
 	uint8_t *ff = NULL;
@@ -493,7 +616,7 @@ nxs_query_prepare_px(const nxs_index_t *idx, const char *query, bool prefixmatch
 		return;
 	}
 	memset(out->tokens, 0, (pr->n + 1) * sizeof(qtok_t));
-	if (prefixmatch && strchr(query, '*')) {
+	if ((prefixmatch && strchr(query, '*')) || (wildcardmatch && strpbrk(query, "*?"))) {
 		for (size_t k = 0; k < pr->n; k++) {
 			n_leaves += pr->items[k].op == 0;
 		}
@@ -519,16 +642,18 @@ nxs_query_prepare_px(const nxs_index_t *idx, const char *query, bool prefixmatch
 		qitem_t *it = &pr->items[k];
 		size_t len, j;
 		char *val;
+		int kind;
 
 		if (it->op != 0) {
 			continue;
 		}
 		len = strlen(it->str);
 		val = it->str;		/* (in the arena; a filter may hand back a malloc'd string) */
-		if (ff && ff[--leaf] && len >= 2 && val[len - 1] == '*') {
-			/* a prefix leaf: no token, never looked up, never fuzzy-matched */
+		if (ff && ff[--leaf] && (kind = leaf_kind(val, len, prefixmatch, wildcardmatch)) >= 0) {
+			/* a prefix or wildcard leaf: no token, never looked up, never fuzzy-matched */
 			out->has_prefix = true;
-			if (prepare_prefix(idx, out, k, val, len - 1) < 0) {
+			if ((kind == QPFX_PREFIX ? prepare_prefix(idx, out, k, val, len - 1) :
+			    prepare_wild(idx, out, k, val, len)) < 0) {
 				free(ff);
 				return;
 			}
