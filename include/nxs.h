@@ -48,7 +48,8 @@ nxs_err_t	nxs_get_error(const nxs_t *, const char **);	/* nxs.h:48 */
 
 /* Parameters (nxs.h:54-67); the query path reads limit / algo / fuzzymatch / total / prefixmatch /
  * prefix_limit / explain / wildcardmatch / wildcard_terms, nxs_index_suggest reads suggest_limit /
- * suggest_maxdist, nxs_index_complete complete_limit, nxs_index_wildcard wildcard_limit */
+ * suggest_maxdist, nxs_index_complete complete_limit, nxs_index_wildcard wildcard_limit, nxs_index_doc_terms
+ * docterms_limit / docterms_mindf, nxs_index_similar similar_terms / similar_mindf / similar_self */
 struct nxs_params;
 typedef struct nxs_params nxs_params_t;
 
@@ -285,6 +286,59 @@ nxs_sugg_t *	nxs_index_wildcard(nxs_index_t *, nxs_params_t *, const char *patte
 int		nxs_index_wildcard_batch(nxs_index_t *, nxs_params_t *,
 		    const char *const *patterns, size_t n,
 		    nxs_sugg_t **out, nxs_err_t *errs);
+
+/*
+ * Similar documents (new; the reference has no "more like this" call, and no call that starts from a doc).
+ *
+ * TERM VECTOR.  For a live doc d of the current snapshot, a ranking function `algo` and mindf >= 1 the
+ * ELIGIBLE terms are the dictionary terms t that have a posting in d, whose live df (the rule of the
+ * suggestions) is at least mindf, and whose float w(t, d) = rank(t, d) under `algo` -- the float "explain"
+ * reports for the pair -- is >= 0 (a negative rank adds nothing to any score, search.c:258).  That last rule
+ * is defensive: the reference's rank() is negative only for tf <= 0 or an average doc length below 1 -- its
+ * BM25 idf is log(1 + (N - df + 0.5) / (df + 0.5)) and its TF-IDF idf log(N / df) + 1 (ranking.c), never
+ * negative, so a term in more than half the docs IS eligible -- and no posting of a live doc, hence no test,
+ * reaches the w < 0 branch on either route.  Their ORDER is w descending as floats, then term id ascending: a total order.  `matches` is
+ * the exact number of eligible terms.
+ *
+ * nxs_index_doc_terms: the first min(k, matches) eligible terms of `doc`, k = "docterms_limit" (uint,
+ * 1..NXS_SUGGEST_MAX, default 5), mindf = "docterms_mindf" (uint >= 1, default 1; out of range:
+ * NXS_ERR_INVALID naming the key), "algo" read as a search reads it (the impacts are materialised on demand,
+ * as by a search), as an nxs_sugg_t: nxs_sugg_get reports the term's bytes, distance = the doc's term count
+ * (tf) and df; nxs_sugg_score reports w (false on an object of the other calls and for i out of range);
+ * nxs_sugg_matches is exact; nxs_sugg_dropped is false.  nxs_sugg_tojson of such an object:
+ *   {"doc_id":7,"terms":[{"term":"...","tf":3,"df":12,"score":1.25},...],"matches":7}
+ * the float as nxs_resp_tojson writes a score, strings with the escaping rules above.  A doc id that is not a
+ * live doc of the snapshot -- never seen, or removed -- is NXS_ERR_MISSING "no such document"; in a batch
+ * that is errs[i], and the call goes on.  nxs_index_doc_terms_batch: as nxs_index_suggest_batch.  Everything
+ * else is nxs_index_complete's: the call re-syncs with the files, is allowed with batches or a pending fuzzy
+ * pass in flight and neither finishes nor reorders them, is local under a communicator, and on a handle from
+ * nxs_index_open_shard fails with NXS_ERR_INVALID "doc_terms is not available on a doc shard".
+ *
+ * nxs_index_similar: "similar_terms" (uint, 1..32, default 8), "similar_mindf" (uint >= 1, default 2: a term
+ * that only d holds has the largest idf and finds nothing; out of range: NXS_ERR_INVALID naming the key),
+ * "similar_self" (bool, default FALSE); "limit", "algo", "total" and "explain" as a search reads them;
+ * "fuzzymatch", "prefixmatch" and "wildcardmatch" are ignored (every term is resolved already).  Let e1..em
+ * be the first min(similar_terms, matches) eligible terms of d at mindf = similar_mindf.  With similar_self
+ * the response is EXACTLY that of the query (e1 OR e2 OR ... OR em), each ei an already resolved term (no
+ * filters, no lookup -- the rule of a prefix leaf): doc set, token set and order, float summation order, ties,
+ * "total" and "explain" follow the rewritten query.  Without it (the default) the query runs at limit + 1,
+ * the entry of d is removed if it is among the results, and the first `limit` are kept; d always matches when
+ * m >= 1, so "total" is the rewritten query's minus 1, and with "explain" the removed result's row goes with
+ * it.  m = 0 is an empty response with total 0, not an error.  limit + 1 must still be a valid limit
+ * (NXS_ERR_INVALID "invalid limit").  A doc that is not live fails with NXS_ERR_MISSING as above; a doc shard
+ * is refused with NXS_ERR_INVALID "similar is not available on a doc shard".  Under a communicator the call
+ * behaves as nxs_index_search_batch of the rewritten queries (the replicas hold one dictionary, df and
+ * postings: every rank derives the same expansions; "total" stays refused there), and the _batch form stands
+ * to batches in flight as nxs_index_search_batch does.  The batch's docs are resolved by one blocking device
+ * pass.
+ */
+nxs_sugg_t *	nxs_index_doc_terms(nxs_index_t *, nxs_params_t *, nxs_doc_id_t doc);
+int		nxs_index_doc_terms_batch(nxs_index_t *, nxs_params_t *, const nxs_doc_id_t *docs, size_t n,
+		    nxs_sugg_t **out, nxs_err_t *errs);
+bool		nxs_sugg_score(const nxs_sugg_t *, unsigned i, float *score);
+nxs_resp_t *	nxs_index_similar(nxs_index_t *, nxs_params_t *, nxs_doc_id_t doc);
+int		nxs_index_similar_batch(nxs_index_t *, nxs_params_t *, const nxs_doc_id_t *docs, size_t n,
+		    nxs_resp_t **resps, nxs_err_t *errs);
 
 /*
  * Batch entry point (new).  Runs `n` queries with one set of params as one

@@ -420,6 +420,43 @@ int		nxsgpu_explain(nxsgpu_index_t *, int algo, uint32_t n_queries,
 void		nxsgpu_explain_profile(nxsgpu_index_t *, double out[NXSGPU_EXPLAIN_PROF], int reset);
 
 /*
+ * ---- term vectors of docs -------------------------------------------------------------
+ *
+ * nxsgpu_doc_terms: for each of n doc ids the ELIGIBLE terms -- a posting in the doc, a live df (the length
+ * of the term's list, what nxsgpu_index_df reports) >= mindf, and the float w = rank(term, doc) under `algo`
+ * (what nxsgpu_explain reports for the pair: d_post[algo] at the posting's position; the REGULAR posting of a
+ * TF-IDF dense term, never its outlier list) >= 0 -- in the order w descending as floats, term id ascending.
+ * Rows of k (1..NXSGPU_DOCTERMS_MAX) entries: term_ids / w / tf / df [n][k], counts[i] = min(k, matches[i]),
+ * matches[i] the exact number of eligible terms, however large; found[i] == 0: doc id i has no ordinal in the
+ * index's doc table and its row is empty (a doc removed by an incremental refresh keeps its ordinal and has no
+ * posting left: found 1, matches 0 -- the host's doc table tells it from a live doc).  A doc id given twice is answered once and copied.  The impacts of `algo`
+ * are materialised on demand, as by a search.  0 / -1.
+ *
+ * There is no forward index: every term's list is asked for the docs (csrc/nxs_docterms.h, on top of
+ * nxs_explain.h's searches).  k_dv_ord finds the ordinals; k_dv_scan -- (part of the term-id range, chunk of
+ * at most 64 docs by ascending ordinal) per wavefront, at most NXS_GPU_DOCTERMS_PARTS (default 512) parts --
+ * matches each list with the chunk from the shorter side, counts eligible hits and keeps a running top-k per
+ * doc in LDS; k_dv_merge selects the k best of a doc's parts and reads w, tf and df at their postings.
+ * Device memory is docs x parts x k keys, never a list of hits; a batch whose partial lists would exceed
+ * NXS_GPU_DOCTERMS_WS (default 64 MiB) is cut into passes of whole chunks.  The pass has a stream, a grow-only workspace, pinned staging and
+ * events of its own: allowed while batches and fuzzy passes are in flight, takes none of their slots;
+ * blocking.  An index that is never asked allocates, uploads and launches nothing.  Under
+ * NXS_GPU_DOCTERMS=host (the cross-check route) the posting arrays are copied back and the same lookups and a
+ * plain sort run on the host.
+ *
+ * nxsgpu_doc_terms_profile: since the last reset -- out[0] calls that reached the device, out[1] / out[2] /
+ * out[3] HIP-event ms of k_dv_ord / k_dv_scan / k_dv_merge (with nxsgpu_set_profiling only), out[4] passes,
+ * out[5] distinct live docs answered on the device, out[6] docs answered on the host, out[7] eligible
+ * (term, doc) pairs counted on the device.
+ */
+#define	NXSGPU_DOCTERMS_MAX	32
+#define	NXSGPU_DOCTERMS_PROF	8
+int		nxsgpu_doc_terms(nxsgpu_index_t *, int algo, const uint64_t *doc_ids, uint32_t n, uint32_t mindf, uint32_t k,
+		    uint32_t *term_ids, float *w, uint32_t *tf, uint32_t *df,	/* rows [n][k] */
+		    uint32_t *counts, uint32_t *matches, uint8_t *found);	/* [n]; found 0 = not a live doc */
+void		nxsgpu_doc_terms_profile(nxsgpu_index_t *, double out[NXSGPU_DOCTERMS_PROF], int reset);
+
+/*
  * ---- host batches as fixed-size records; query sharding over several GPUs ----
  *
  * The reference scales out by running independent worker processes

@@ -94,6 +94,8 @@ NXS_H_SYMBOLS = [
     "nxs_index_complete", "nxs_index_complete_batch",
     "nxs_index_wildcard", "nxs_index_wildcard_batch",
     "nxs_resp_tokens", "nxs_resp_token", "nxs_resp_explain",
+    "nxs_index_doc_terms", "nxs_index_doc_terms_batch", "nxs_sugg_score",
+    "nxs_index_similar", "nxs_index_similar_batch",
 ]
 # csrc/nxs_hooks.h: test hooks + bench accessors, only in builds with -DNXS_TEST_HOOKS (the default)
 NXS_HOOK_SYMBOLS = ["nxs_index_device", "nxs_index_host_profile", "nxs_index_shard_info", "nxs_test_pool", "nxs_test_assemble",
@@ -104,7 +106,9 @@ NXS_HOOK_SYMBOLS = ["nxs_index_device", "nxs_index_host_profile", "nxs_index_sha
                     "nxs_test_wild_match", "nxs_test_wild_match_inl", "nxs_test_wild_host", "nxs_test_wild_params",
                     "nxs_test_wild_normalize", "nxs_test_wild_build", "nxs_test_wild_query",
                     "nxs_test_explain_params", "nxs_test_resp_build", "nxs_test_explain_search",
-                    "nxs_test_explain_ordinal"]
+                    "nxs_test_explain_ordinal",
+                    "nxs_test_docterms_params", "nxs_test_docterms_build", "nxs_test_docterms_lane",
+                    "nxs_test_docterms_key", "nxs_test_similar_drop"]
 NXS_GPU_H_SYMBOLS = [
     "nxsgpu_device_count", "nxsgpu_last_error", "nxsgpu_index_create",
     "nxsgpu_index_destroy", "nxsgpu_index_df", "nxsgpu_index_postings",
@@ -126,6 +130,7 @@ NXS_GPU_H_SYMBOLS = [
     "nxsgpu_complete", "nxsgpu_complete_profile",
     "nxsgpu_wildcard", "nxsgpu_wildcard_profile",
     "nxsgpu_explain", "nxsgpu_explain_profile",
+    "nxsgpu_doc_terms", "nxsgpu_doc_terms_profile",
 ]
 
 _lib = None
@@ -280,6 +285,38 @@ def lib():
     L.nxsgpu_wildcard.argtypes = [vp, cp, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32,
                                   C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                   C.POINTER(C.c_uint32)]
+    L.nxs_index_doc_terms.restype = vp
+    L.nxs_index_doc_terms.argtypes = [vp, vp, C.c_uint64]
+    L.nxs_index_doc_terms_batch.restype = C.c_int
+    L.nxs_index_doc_terms_batch.argtypes = [vp, vp, C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(vp), C.POINTER(C.c_int)]
+    L.nxs_sugg_score.restype = C.c_bool
+    L.nxs_sugg_score.argtypes = [vp, C.c_uint, C.POINTER(C.c_float)]
+    L.nxs_index_similar.restype = vp
+    L.nxs_index_similar.argtypes = [vp, vp, C.c_uint64]
+    L.nxs_index_similar_batch.restype = C.c_int
+    L.nxs_index_similar_batch.argtypes = [vp, vp, C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(vp), C.POINTER(C.c_int)]
+    L.nxsgpu_doc_terms.restype = C.c_int
+    L.nxsgpu_doc_terms.argtypes = [vp, C.c_int, C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, C.c_uint32,
+                                   C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_uint32),
+                                   C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                   C.POINTER(C.c_uint8)]
+    L.nxsgpu_doc_terms_profile.restype = None
+    L.nxsgpu_doc_terms_profile.argtypes = [vp, C.POINTER(C.c_double), C.c_int]
+    if hasattr(L, "nxs_test_docterms_params"):
+        L.nxs_test_docterms_params.restype = C.c_int
+        L.nxs_test_docterms_params.argtypes = [vp, vp, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint),
+                                               C.POINTER(C.c_uint), C.POINTER(C.c_int)]
+        L.nxs_test_docterms_build.restype = vp
+        L.nxs_test_docterms_build.argtypes = [C.c_uint64, C.c_uint64, C.c_uint, C.POINTER(C.c_char_p),
+                                              C.POINTER(C.c_size_t), C.POINTER(C.c_uint), C.POINTER(C.c_uint64),
+                                              C.POINTER(C.c_float)]
+        L.nxs_test_docterms_lane.restype = C.c_int
+        L.nxs_test_docterms_lane.argtypes = [C.POINTER(C.c_uint64), C.c_uint64, C.c_bool, C.c_uint32,
+                                             C.POINTER(C.c_uint32), C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]
+        L.nxs_test_docterms_key.restype = C.c_uint64
+        L.nxs_test_docterms_key.argtypes = [C.c_float, C.c_uint32]
+        L.nxs_test_similar_drop.restype = None
+        L.nxs_test_similar_drop.argtypes = [vp, C.c_uint64, C.c_uint64]
     L.nxsgpu_wildcard_profile.restype = None
     L.nxsgpu_wildcard_profile.argtypes = [vp, C.POINTER(C.c_double), C.c_int]
     L.nxsgpu_explain_profile.restype = None
@@ -567,6 +604,33 @@ class Suggestions(list):
     word)."""
     matches = 0
     dropped = False
+
+
+class DocTerms(list):
+    """The term vector of one doc (nxs_sugg_t of nxs_index_doc_terms): [(term: bytes, tf, df, score), ...] best
+    first, with `.matches` = the exact number of eligible terms."""
+    matches = 0
+
+
+def _drain_docterms(sg, json=False):
+    """nxs_sugg_t of the term-vector kind -> DocTerms (or its JSON text); releases the object"""
+    L = lib()
+    try:
+        if json:
+            n = C.c_size_t()
+            return _take(L.nxs_sugg_tojson(sg, C.byref(n)))
+        out = DocTerms()
+        term, ln, tf, df, sc = C.c_void_p(), C.c_size_t(), C.c_uint(), C.c_uint64(), C.c_float()
+        i = 0
+        while L.nxs_sugg_get(sg, i, C.byref(term), C.byref(ln), C.byref(tf), C.byref(df)):
+            assert L.nxs_sugg_score(sg, i, C.byref(sc))
+            out.append((C.string_at(term.value, ln.value), tf.value, df.value, sc.value))
+            i += 1
+        assert i == L.nxs_sugg_count(sg) and not L.nxs_sugg_dropped(sg)
+        out.matches = L.nxs_sugg_matches(sg)
+        return out
+    finally:
+        L.nxs_sugg_release(sg)
 
 
 def _drain_sugg(sg, json=False):
@@ -962,6 +1026,79 @@ class Index:
         return {"passes": int(out[0]), "ms": out[1], "range_ms": out[2], "match_ms": out[3], "merge_ms": out[4],
                 "entries": int(out[5]), "host_patterns": int(out[6]), "builds": int(out[7]),
                 "device_patterns": int(out[8])}
+
+    def doc_terms(self, docs, limit=None, mindf=None, algo=None, json=False):
+        """nxs_index_doc_terms_batch(): for every doc id the dictionary terms the doc holds whose live df is at
+        least `mindf` (default 1) and whose rank under `algo` is not negative, best `limit` (1..32, default 5)
+        by score descending, then term id -> a list of DocTerms, one per doc, entries (term, tf, df, score),
+        `.matches` exact (an NxsError instance in the slot of a doc that is not live); json: their JSON
+        texts."""
+        L = lib()
+        n = len(docs)
+        p = None
+        if limit is not None or mindf is not None or algo is not None:
+            p = L.nxs_params_create()
+            if limit is not None:
+                L.nxs_params_set_uint(p, b"docterms_limit", limit)
+            if mindf is not None:
+                L.nxs_params_set_uint(p, b"docterms_mindf", mindf)
+            if algo is not None:
+                L.nxs_params_set_str(p, b"algo", _b(algo))
+        out = (C.c_void_p * max(n, 1))()
+        errs = (C.c_int * max(n, 1))()
+        ds = (C.c_uint64 * max(n, 1))(*docs)
+        try:
+            r = L.nxs_index_doc_terms_batch(self._h, p, ds, n, out, errs)
+        finally:
+            if p:
+                L.nxs_params_release(p)
+        if r < 0:
+            self.nxs._raise()
+        return [_drain_docterms(out[i], json) if out[i] else NxsError(errs[i], "doc %d failed" % i) for i in range(n)]
+
+    def similar(self, docs, limit=None, algo=None, terms=None, mindf=None, include_self=None, total=False,
+                explain=False):
+        """nxs_index_similar_batch(): for every doc id the docs most like it -- the results of the OR of its
+        `terms` (1..32, default 8) best terms of df >= `mindf` (default 2), without the doc itself unless
+        `include_self` -> result lists as search_batch returns them (an NxsError instance in the slot of a doc
+        that is not live)."""
+        L = lib()
+        n = len(docs)
+        p = _make_params(limit, algo, None, total, explain=explain)
+        if terms is not None or mindf is not None or include_self is not None:
+            p = p or L.nxs_params_create()
+            if terms is not None:
+                L.nxs_params_set_uint(p, b"similar_terms", terms)
+            if mindf is not None:
+                L.nxs_params_set_uint(p, b"similar_mindf", mindf)
+            if include_self is not None:
+                L.nxs_params_set_bool(p, b"similar_self", bool(include_self))
+        resps = (C.c_void_p * max(n, 1))()
+        errs = (C.c_int * max(n, 1))()
+        ds = (C.c_uint64 * max(n, 1))(*docs)
+        try:
+            r = L.nxs_index_similar_batch(self._h, p, ds, n, resps, errs)
+        finally:
+            if p:
+                L.nxs_params_release(p)
+        if r < 0:
+            self.nxs._raise()
+        out = []
+        for i in range(n):
+            if resps[i]:
+                out.append(_drain(resps[i], explain))
+                L.nxs_resp_release(resps[i])
+            else:
+                out.append(NxsError(errs[i], "doc %d failed" % i))
+        return out
+
+    def doc_terms_profile(self, reset=False):
+        """nxsgpu_doc_terms_profile(): calls that reached the device, HIP-event ms per kernel (profiling on),
+        passes, distinct docs answered on the device / docs answered on the host, eligible pairs counted."""
+        out = (C.c_double * 8)()
+        lib().nxsgpu_doc_terms_profile(self.device, out, 1 if reset else 0)
+        return {"calls": int(out[0]), "ord_ms": out[1], "scan_ms": out[2], "merge_ms": out[3], "passes": int(out[4]),
+                "device_docs": int(out[5]), "host_docs": int(out[6]), "eligible": int(out[7])}
 
     def explain_profile(self, reset=False):
         """nxsgpu_explain_profile(): explain passes, HIP-event ms of k_explain (profiling on), (result, token)

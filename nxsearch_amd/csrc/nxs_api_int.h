@@ -57,6 +57,10 @@ typedef struct {
 	bool		wildcardmatch;	/* "wildcardmatch": a free-form leaf with a `*` or `?` stands for its best matching terms */
 	unsigned	wildcard_terms;	/* "wildcard_terms": how many of them (1..NXS_PREFIX_MAX, default 8) */
 	bool		explain;	/* "explain": per result and token the term count and the score contribution */
+	/* nxs_index_similar only */
+	unsigned	similar_terms;	/* "similar_terms": expansions of the source doc (1..NXS_PREFIX_MAX, default 8) */
+	unsigned	similar_mindf;	/* "similar_mindf": the df floor of an expansion (>= 1, default 2) */
+	bool		similar_self;	/* "similar_self": the source doc stays among the results */
 } search_params_t;
 
 int	get_ranking_func_id(const char *name);
@@ -97,6 +101,7 @@ typedef struct {
 int	slab_begin(slab_builder_t *, size_t n, size_t total);
 void	slab_free(struct resp_slab *);
 size_t	json_str(char *out, const char *s, size_t n);
+size_t	fmt_real(char *out, double v);		/* a JSON real as nxs_resp_tojson writes a score; out: room for 40 bytes */
 
 /* response i of the slab: `count` results to be filled in by the caller (per query: inline in its callers' units) */
 static inline nxs_resp_t *
@@ -166,11 +171,12 @@ struct late_half {
 };
 
 void	plan_cache_destroy(struct plan_cache *);
-int	plan_front(nxs_index_t *, const search_params_t *, const char *const *queries, size_t n, qprep_t *prep,
-	    fz_set_t *fz);
+int	plan_front(nxs_index_t *, const search_params_t *, const char *const *queries, const nxs_doc_id_t *docs, size_t n,
+	    qprep_t *prep, fz_set_t *fz);
 void	plan_back(nxs_index_t *, const search_params_t *, const char *const *queries, size_t n, qprep_t *prep,
 	    const fz_set_t *fz);
-int	plan_batch(nxs_index_t *, const search_params_t *, const char *const *queries, size_t n, qprep_t *prep);
+int	plan_batch(nxs_index_t *, const search_params_t *, const char *const *queries, const nxs_doc_id_t *docs, size_t n,
+	    qprep_t *prep);
 void	fz_set_free(fz_set_t *);
 struct late_half *late_make(const search_params_t *, fz_set_t *fz, const char *const *queries, size_t n,
 	    const qprep_t *prep);
@@ -190,6 +196,23 @@ nxs_pend_t *pend_oldest(nxs_index_t *);
 int	resync_before_batch(nxs_index_t *);
 int	late_finish(nxs_index_t *);
 void	index_drain(nxs_index_t *);
+
+/* ---- nxs_lookup.c ---------------------------------------------------------------------- */
+
+/* the rows nxsgpu_doc_terms fills for n docs at k terms each */
+typedef struct {
+	uint32_t	*ids, *tf, *df;	/* [n * k] */
+	float *		w;		/* [n * k] */
+	uint32_t	*counts, *matches;	/* [n] */
+	uint8_t *	found;		/* [n] 1 = a live doc of the snapshot */
+} docterms_rows_t;
+
+/* the term vectors of docs[0 .. n): allocates the rows, runs the device pass, and clears `found` for a doc that
+ * has been removed (it keeps its ordinal; the host's doc table knows).  0, or -1 with the error declared and
+ * nothing left to free */
+int	docterms_rows(nxs_index_t *, int algo, const nxs_doc_id_t *docs, size_t n, unsigned mindf, unsigned k,
+	    docterms_rows_t *);
+void	docterms_rows_free(docterms_rows_t *);
 
 #pragma GCC visibility pop
 

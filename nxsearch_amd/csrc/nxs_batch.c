@@ -347,13 +347,17 @@ late_finish(nxs_index_t *idx)
 	return ret;
 }
 
-int
-nxs_index_search_batch_begin(nxs_index_t *idx, nxs_params_t *params,
-    const char *const *queries, size_t n)
+/*
+ * The body of a _begin, after the params have been read.  The batch is n query strings -- or, docs != NULL
+ * (queries is NULL then), nxs_index_similar's: query i is the doc leaf of docs[i], resolved with the batch's
+ * other docs in plan_front; such a batch has no fuzzy misses and is never left with a late half.
+ */
+static int
+batch_begin(nxs_index_t *idx, const search_params_t *spp, const char *const *queries, const nxs_doc_id_t *docs, size_t n)
 {
 	nxs_t *nxs = idx->nxs;
 	nxs_pend_t *pd = NULL;
-	search_params_t sp;
+	const search_params_t sp = *spp;
 	uint32_t *status = NULL;
 	uint64_t lo = 0, hi = n;
 	size_t nl;
@@ -363,10 +367,6 @@ nxs_index_search_batch_begin(nxs_index_t *idx, nxs_params_t *params,
 	nxs_pend_t *old;
 	int ret = -1;
 
-	nxs_clear_error(nxs);
-	if (get_search_params(idx, params, &sp) == -1) {
-		return -1;
-	}
 	/* (totals would have to travel in the record blocks all ranks agree on: a follow-up, include/nxs.h;
 	 * every rank passes the same params, so every rank refuses) */
 	if (sp.total && (idx->comm || idx->emu_world > 1)) {
@@ -426,7 +426,7 @@ nxs_index_search_batch_begin(nxs_index_t *idx, nxs_params_t *params,
 		goto out;
 	}
 	t0 = now_s();
-	if (plan_front(idx, &sp, queries + lo, nl, pd->prep, &fz) == -1 ||
+	if (plan_front(idx, &sp, queries ? queries + lo : NULL, docs ? docs + lo : NULL, nl, pd->prep, &fz) == -1 ||
 	    (idx->test_fail_begin && idx->test_fail_begin-- == 1 &&
 	    (nxs_decl_err(nxs, NXS_ERR_SYSTEM, "injected failure (test)"), true))) {
 		(void)late_finish(idx);
@@ -523,7 +523,7 @@ nxs_index_search_batch_begin(nxs_index_t *idx, nxs_params_t *params,
 		(void)late_complete(idx, old);
 	}
 	t1 = now_s();
-	plan_back(idx, &sp, queries + lo, nl, pd->prep, &fz);
+	plan_back(idx, &sp, queries ? queries + lo : NULL, nl, pd->prep, &fz);
 	idx->hp_back += now_s() - t1;
 	if (sp.explain && pd->world > 1 && !idx->shard_local) {
 		/*
@@ -536,8 +536,9 @@ nxs_index_search_batch_begin(nxs_index_t *idx, nxs_params_t *params,
 		if (!pd->xprep) {
 			nxs_decl_err(nxs, NXS_ERR_SYSTEM, "out of memory");
 		}
-		if (!pd->xprep || (lo && plan_batch(idx, &sp, queries, lo, pd->xprep) == -1) ||
-		    (hi < n && plan_batch(idx, &sp, queries + hi, n - hi, pd->xprep + hi) == -1)) {
+		if (!pd->xprep || (lo && plan_batch(idx, &sp, queries, docs, lo, pd->xprep) == -1) ||
+		    (hi < n && plan_batch(idx, &sp, queries ? queries + hi : NULL, docs ? docs + hi : NULL, n - hi,
+		    pd->xprep + hi) == -1)) {
 			if (collective) {
 				goto abort_collective;
 			}
@@ -606,6 +607,19 @@ abort_collective:
 		free(msg);
 	}
 	goto out;
+}
+
+int
+nxs_index_search_batch_begin(nxs_index_t *idx, nxs_params_t *params,
+    const char *const *queries, size_t n)
+{
+	search_params_t sp;
+
+	nxs_clear_error(idx->nxs);
+	if (get_search_params(idx, params, &sp) == -1) {
+		return -1;
+	}
+	return batch_begin(idx, &sp, queries, NULL, n);
 }
 
 /* exact path (nxsgpu_search / nxsgpu_search_wide) for the given local queries */
@@ -1232,6 +1246,120 @@ nxs_index_search_batch(nxs_index_t *idx, nxs_params_t *params,
 	}
 	return nxs_index_search_batch_end(idx, resps, errs);
 }
+
+/* ---- similar documents (nxs_index_similar) -------------------------------------------- */
+
+/*
+ * The source doc out of a finished response that ran at limit + 1: its entry goes if it is among the results
+ * (ids, scores and the explain row move up within the response's own arrays), then the first `limit` stay.
+ * The doc matches its own expansions whenever there are any, so a total that counted something counted it.
+ */
+static void
+similar_drop(nxs_resp_t *r, nxs_doc_id_t doc, uint64_t limit)
+{
+	unsigned at = 0;
+
+	while (at < r->count && r->ids[at] != doc) {
+		at++;
+	}
+	if (at < r->count) {
+		const size_t tail = r->count - at - 1;
+
+		memmove(r->ids + at, r->ids + at + 1, tail * sizeof(*r->ids));
+		memmove(r->scores + at, r->scores + at + 1, tail * sizeof(*r->scores));
+		if (r->n_tok && r->ex_tf && r->ex_imp) {
+			/* (the rows live in the slab's explain block, which this response's batch owns) */
+			uint32_t *tf = (uint32_t *)(uintptr_t)r->ex_tf;
+			float *imp = (float *)(uintptr_t)r->ex_imp;
+
+			memmove(tf + (size_t)at * r->n_tok, tf + (size_t)(at + 1) * r->n_tok, tail * r->n_tok * sizeof(*tf));
+			memmove(imp + (size_t)at * r->n_tok, imp + (size_t)(at + 1) * r->n_tok, tail * r->n_tok * sizeof(*imp));
+		}
+		r->count--;
+	}
+	if (r->has_total && r->total) {
+		r->total--;
+	}
+	if (r->count > limit) {
+		r->count = (unsigned)limit;
+	}
+	r->iter = 0;
+}
+
+int
+nxs_index_similar_batch(nxs_index_t *idx, nxs_params_t *params, const nxs_doc_id_t *docs, size_t n,
+    nxs_resp_t **resps, nxs_err_t *errs)
+{
+	nxs_t *nxs = idx->nxs;
+	search_params_t sp;
+	uint64_t limit;
+	int ret;
+
+	nxs_clear_error(nxs);
+	if (pend_oldest(idx)) {
+		nxs_decl_err(nxs, NXS_ERR_INVALID, "finish the batches in flight first (nxs_index_search_batch_end)");
+		return -1;
+	}
+	outs_clear(resps, errs, n);
+	if (get_search_params(idx, params, &sp) == -1) {
+		return -1;
+	}
+	/* (a shard's postings are its own: a follow-up, include/nxs.h) */
+	if (idx->n_shards) {
+		nxs_decl_err(nxs, NXS_ERR_INVALID, "similar is not available on a doc shard");
+		return -1;
+	}
+	limit = sp.limit;
+	if (!sp.similar_self) {
+		if (sp.limit + 1 > UINT_MAX) {
+			nxs_decl_err(nxs, NXS_ERR_INVALID, "invalid limit");
+			return -1;
+		}
+		sp.limit++;
+	}
+	/* every term is resolved already */
+	sp.fuzzymatch = false;
+	sp.prefixmatch = false;
+	sp.wildcardmatch = false;
+	if (batch_begin(idx, &sp, NULL, docs, n) != 0) {
+		return -1;
+	}
+	ret = nxs_index_search_batch_end(idx, resps, errs);
+	for (size_t i = 0; ret >= 0 && !sp.similar_self && i < n; i++) {
+		if (resps[i]) {
+			similar_drop(resps[i], docs[i], limit);
+		}
+	}
+	return ret;
+}
+
+nxs_resp_t *
+nxs_index_similar(nxs_index_t *idx, nxs_params_t *params, nxs_doc_id_t doc)
+{
+	nxs_resp_t *resp = NULL;
+	nxsgpu_comm_t *comm = idx->comm;
+	int r;
+
+	idx->comm = NULL;	/* one doc is never sharded (as nxs_index_search) */
+	r = nxs_index_similar_batch(idx, params, &doc, 1, &resp, NULL);
+	idx->comm = comm;
+	if (r != 0) {
+		if (resp) {
+			nxs_resp_release(resp);
+		}
+		return NULL;
+	}
+	return resp;
+}
+
+#ifdef NXS_TEST_HOOKS
+/* the self-removal of nxs_index_similar on a response handed in (built by nxs_test_resp_build) */
+void
+nxs_test_similar_drop(nxs_resp_t *r, uint64_t doc, uint64_t limit)
+{
+	similar_drop(r, doc, limit);
+}
+#endif
 
 /* nxs_index_search: search.c:285-342 (one query = a batch of one) */
 nxs_resp_t *

@@ -186,7 +186,7 @@ docshard_search(nxs_index_t *const *local, unsigned n_local, unsigned n_shards, 
 		goto out;
 	}
 	/* the term dictionary and the BK-tree are the same on every shard */
-	if (plan_batch(idx0, &sp, queries, n, prep) == -1) {
+	if (plan_batch(idx0, &sp, queries, NULL, n, prep) == -1) {
 		goto out;
 	}
 	for (size_t i = 0; i < n; i++) {

@@ -136,6 +136,12 @@ cfg_from_env(gpu_cfg_t &c)
 		c.wild_host = e && !strcmp(e, "host");
 	}
 	c.wild_parts = (uint32_t)u64("NXS_GPU_WILD_PARTS", 64, 1, 1024);
+	{
+		const char *e = getenv("NXS_GPU_DOCTERMS");
+		c.docterms_host = e && !strcmp(e, "host");
+	}
+	c.docterms_parts = (uint32_t)u64("NXS_GPU_DOCTERMS_PARTS", 512, 1, 4096);
+	c.docterms_ws = u64("NXS_GPU_DOCTERMS_WS", 64ull << 20, 1, 1ull << 32);
 }
 
 /* ------------------------------------------------------------------ */
@@ -666,6 +672,7 @@ nxsgpu_index_destroy(nxsgpu_index_t *ix)
 	wc_free(ix);
 	px_free(ix);
 	ex_free(ix);
+	dv_free(ix);
 	bk_aux_free(ix);
 	(void)hipFree(ix->ws);
 	(void)hipFree(ix->fz);

@@ -34,6 +34,8 @@
  *                         it with a running top-k per workgroup (k_wc_match), the parts merged (k_wc_merge)
  *  nxs_gpu_explain.hip    k_explain: per returned doc and query token the term count and the float the
  *                         token added to the score, looked up in the CSR (nxs_explain.h)
+ *  nxs_gpu_docterms.hip   term vectors of docs: every term's list asked for a chunk of docs (k_dv_scan, nxs_docterms.h),
+ *                         a running top-k per doc and part, the parts merged (k_dv_merge)
  *  nxs_gpu_plan.hip       host only: query classes, the work list (build_worklist) and
  *                         the layout of a batch's arrays (batch_layout)
  *  nxs_gpu_search.hip     kernel dispatch, blocking search, batches in flight
@@ -187,6 +189,12 @@ struct gpu_cfg_t {
 					 * each (k_wc_match); its partial top-k lists are [parts][k] keys */
 	uint64_t	explain_rows;	/* NXS_GPU_EXPLAIN_ROWS (2 M): (result, token) cells per explain pass -- 17 bytes of workspace a
 					 * cell at most (one-token queries), 36 MB */
+	bool		docterms_host;	/* NXS_GPU_DOCTERMS=host: every term vector from the host lookups (nxs_docterms.h) over a copy of the
+					 * posting arrays: the cross-check */
+	uint32_t	docterms_parts;	/* NXS_GPU_DOCTERMS_PARTS (512): the term-id range is cut into at most this many parts, one wavefront
+					 * each per chunk of 64 docs (k_dv_scan); its partial top-k lists are [docs][parts][k] keys */
+	uint64_t	docterms_ws;	/* NXS_GPU_DOCTERMS_WS (64 MiB): bytes of partial lists per pass; a larger batch is cut into passes
+					 * of whole chunks (one chunk at least) */
 };
 enum : uint32_t { COUNT_AUTO = 0, COUNT_TILE = 1, COUNT_REQ = 2, COUNT_SCAN = 3 };
 
@@ -410,6 +418,8 @@ struct nxsgpu_index {
 	struct wc_state_t *wc;
 	/* explanations (nxsgpu_explain, nxs_gpu_explain.hip): stream, workspace, staging; nothing until the first call */
 	struct ex_state_t *ex;
+	/* term vectors of docs (nxsgpu_doc_terms, nxs_gpu_docterms.hip): the same; nothing until the first call */
+	struct dv_state_t *dv;
 };
 
 static inline uint32_t __device__ __host__
@@ -678,6 +688,9 @@ void	wc_free(nxsgpu_index_t *ix);		/* everything nxsgpu_wildcard has built (inde
 
 /* ---- nxs_gpu_explain.hip ---- */
 void	ex_free(nxsgpu_index_t *ix);		/* everything nxsgpu_explain has built (index destroy) */
+
+/* ---- nxs_gpu_docterms.hip ---- */
+void	dv_free(nxsgpu_index_t *ix);		/* everything nxsgpu_doc_terms has built (index destroy) */
 
 /* ---- nxs_gpu_plan.hip ---- */
 void	delete_worklist(worklist_t *);

@@ -14,6 +14,7 @@
 #include "nxs_complete.h"
 #include "nxs_wild.h"
 #include "nxs_explain.h"
+#include "nxs_docterms.h"
 
 char *
 nxs_test_query_repr(const char *query, char **errmsg)
@@ -218,6 +219,55 @@ nxs_test_explain_search(const uint64_t *dt, uint64_t n, bool bitmap, uint32_t n_
 	free(bm);
 	free(rk);
 	return 0;
+}
+
+/*
+ * nxs_dv_term (nxs_docterms.h) over the list dt[0 .. n) and the chunk ords[0 .. nd) (ascending, distinct, below
+ * n_docs, nd <= NXS_DV_CHUNK); by_posting: 1 / 0 force the side, -1 = nxs_dv_by_posting's rule.  -> the side
+ * taken (1: by posting), -1: out of memory / a chunk that is too long
+ */
+int
+nxs_test_docterms_lane(const uint64_t *dt, uint64_t n, bool bitmap, uint32_t n_docs, const uint32_t *ords, uint32_t nd,
+    int by_posting, uint64_t *pos)
+{
+	const uint64_t words = ((uint64_t)n_docs + 4095) / 4096;
+	uint64_t *bm = NULL;
+	uint32_t *rk = NULL;
+	bool side;
+
+	if (nd > NXS_DV_CHUNK) {
+		return -1;
+	}
+	if (bitmap) {
+		bm = calloc(words ? words : 1, sizeof(uint64_t));
+		rk = calloc(words + 1, sizeof(uint32_t));
+		if (!bm || !rk) {
+			free(bm);
+			free(rk);
+			return -1;
+		}
+		for (uint64_t w = 0, i = 0; w <= words; w++) {
+			while (i < n && ((dt[i] >> 32) >> 12) < w) {
+				i++;
+			}
+			rk[w] = (uint32_t)i;
+		}
+		for (uint64_t i = 0; i < n; i++) {
+			const uint32_t d = (uint32_t)(dt[i] >> 32);
+			bm[d >> 12] |= UINT64_C(1) << ((d >> 6) & 63);
+		}
+	}
+	side = by_posting < 0 ? nxs_dv_by_posting(n, nd, bitmap) : by_posting != 0;
+	nxs_dv_term(dt, 0, n, bm, rk, ords, nd, side, pos);
+	free(bm);
+	free(rk);
+	return side;
+}
+
+uint64_t
+nxs_test_docterms_key(float w, uint32_t term)
+{
+	return nxs_dv_key(w, term);
 }
 
 /* nxs_ex_ordinal for every q[i] over ids[0 .. n) (UINT64_MAX: not a live doc) */

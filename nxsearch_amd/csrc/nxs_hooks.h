@@ -131,5 +131,21 @@ int		nxs_test_explain_search(const uint64_t *dt, uint64_t n, bool bitmap, uint32
 		    const uint32_t *docs, size_t nd, uint64_t *pos, uint64_t *lower);
 void		nxs_test_explain_ordinal(const uint64_t *ids, uint64_t n, const uint64_t *q, size_t nq, uint64_t *out);
 
+
+/* similar documents: the parameters as nxs_index_doc_terms / nxs_index_similar read them (0, or -1 with the error
+ * declared), an nxs_sugg_t of the term-vector kind built by hand, the lookups of the shared header
+ * nxs_docterms.h over a list handed in (one list against one chunk of ascending ordinals: pos[j] = the position
+ * of ordinal j's posting, UINT64_MAX = absent; by_posting: 1 / 0 force the side the searches start from, -1 the
+ * rule of the kernel; bitmap: through a block bitmap + rank directory built from the list; -> the side taken),
+ * nxs_dv_key, and nxs_index_similar's self-removal on a response built by nxs_test_resp_build */
+int		nxs_test_docterms_params(nxs_t *, nxs_params_t *, unsigned *k, unsigned *mindf, unsigned *similar_terms,
+		    unsigned *similar_mindf, int *similar_self);
+nxs_sugg_t *	nxs_test_docterms_build(uint64_t doc, uint64_t matches, unsigned count, const uint8_t *const *terms,
+		    const size_t *lens, const unsigned *tfs, const uint64_t *dfs, const float *scores);
+int		nxs_test_docterms_lane(const uint64_t *dt, uint64_t n, bool bitmap, uint32_t n_docs, const uint32_t *ords,
+		    uint32_t nd, int by_posting, uint64_t *pos);
+uint64_t	nxs_test_docterms_key(float w, uint32_t term);
+void		nxs_test_similar_drop(nxs_resp_t *, uint64_t doc, uint64_t limit);
+
 #endif /* NXS_TEST_HOOKS */
 #endif /* NXS_HOOKS_H */

@@ -200,6 +200,7 @@ int	nxs_shard_merge(nxs_index_t *, nxs_delta_t *);
 void	nxs_delta_abort(nxs_index_t *, nxs_delta_t *);
 int	nxs_shard_rebuild(nxs_index_t *, const nxs_snap_t *);
 uint32_t nxs_term_lookup(const nxs_index_t *, const uint8_t *val, size_t len);
+bool	nxs_index_doc_live(const nxs_index_t *, uint64_t doc_id) __attribute__((visibility("hidden")));
 
 /* flattened BK-tree built on the host (exported for the CPU-side tests) */
 typedef struct {
@@ -287,7 +288,12 @@ typedef struct {
  * `val` is the normalised pattern (nxs_wild_normalize), the expansions come from nxsgpu_wildcard and number
  * min(wildcard_terms, matches).
  */
-enum { QPFX_PREFIX = 0, QPFX_WILD = 1 };
+/*
+ * A doc leaf (nxs_index_similar: a program of this one leaf, nxs_query_prepare_doc): `val` carries the source
+ * doc's id in decimal, the expansions come from nxsgpu_doc_terms -- the first min(similar_terms, matches)
+ * eligible terms of the doc's term vector at mindf = similar_mindf.  Never plan-cached, never fuzzy-matched.
+ */
+enum { QPFX_PREFIX = 0, QPFX_WILD = 1, QPFX_DOC = 2 };
 typedef struct {
 	size_t		item;		/* the leaf: index into parse.items */
 	int		kind;		/* QPFX_* */
@@ -320,6 +326,8 @@ typedef struct qprep {
 } qprep_t;
 
 void	nxs_query_prepare(const nxs_index_t *, const char *query, qprep_t *out);
+/* the query of nxs_index_similar: one doc leaf (QPFX_DOC), no token */
+void	nxs_query_prepare_doc(nxs_doc_id_t doc, qprep_t *out);
 /* the same; prefixmatch: a leaf from a free-form string that ends in `*` (and is longer) is a prefix leaf --
  * kept out of the token list, recorded in out->pfx */
 void	nxs_query_prepare_px(const nxs_index_t *, const char *query, bool prefixmatch, qprep_t *out);

@@ -976,6 +976,16 @@ ord_of(const nxs_index_t *idx, uint64_t doc_id)
 	return (lo < idx->n_ord && idx->h_doc_ids[lo] == doc_id) ? (int64_t)lo : -1;
 }
 
+/* is doc_id a live doc of the snapshot the index serves?  (A doc removed by an incremental refresh keeps its
+ * ordinal in the doc table, on the host and on the device, and has no posting left.) */
+bool
+nxs_index_doc_live(const nxs_index_t *idx, uint64_t doc_id)
+{
+	const int64_t o = ord_of(idx, doc_id);
+
+	return o >= 0 && idx->h_alive[o] == 1;
+}
+
 /*
  * The reference re-syncs appended data before every search (search.c:309-312:
  * idx_terms_sync + idx_dtmap_sync(PARTIAL)).  Here: consume the term blocks and

@@ -1,7 +1,8 @@
 /*
  * nxs_lookup.c -- dictionary lookups by string: spelling suggestions
  * (nxs_index_suggest), prefix completions (nxs_index_complete) and wildcard
- * matches (nxs_index_wildcard), and the object all three return (nxs_sugg_t).
+ * matches (nxs_index_wildcard); by doc: its term vector (nxs_index_doc_terms);
+ * and the object all four return (nxs_sugg_t).
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -17,8 +18,9 @@
 typedef struct {
 	char *		term;		/* owned by the object, NUL-terminated */
 	size_t		len;
-	unsigned	dist;
+	unsigned	dist;		/* (a term vector's: the doc's term count) */
 	uint64_t	df;
+	float		score;		/* a term vector's: rank(term, doc) */
 } sugg_item_t;
 
 struct nxs_sugg {
@@ -26,13 +28,14 @@ struct nxs_sugg {
 	size_t		token_len;
 	bool		dropped;
 	int		kind;		/* SUGG_*: by nxs_index_complete / _wildcard `token` is the prefix / the pattern, the
-					 * JSON has its own shape */
+					 * JSON has its own shape; by nxs_index_doc_terms there is no string but doc_id */
+	uint64_t	doc_id;
 	uint64_t	matches;
 	unsigned	count;
 	sugg_item_t	items[];
 };
 
-enum { SUGG_SUGGEST = 0, SUGG_COMPLETE = 1, SUGG_WILD = 2 };
+enum { SUGG_SUGGEST = 0, SUGG_COMPLETE = 1, SUGG_WILD = 2, SUGG_DOC = 3 };
 
 /* one block: the object, its items, the strings */
 static nxs_sugg_t *
@@ -57,6 +60,7 @@ sugg_build(const char *token, size_t token_len, bool dropped, uint64_t matches, 
 	str += token_len + 1;
 	sg->dropped = dropped;
 	sg->kind = SUGG_SUGGEST;
+	sg->doc_id = 0;
 	sg->matches = matches;
 	sg->count = count;
 	for (unsigned i = 0; i < count; i++) {
@@ -64,6 +68,7 @@ sugg_build(const char *token, size_t token_len, bool dropped, uint64_t matches, 
 		sg->items[i].len = lens[i];
 		sg->items[i].dist = dists[i];
 		sg->items[i].df = dfs[i];
+		sg->items[i].score = 0.0f;
 		memcpy(str, terms[i], lens[i]);
 		str[lens[i]] = '\0';
 		str += lens[i] + 1;
@@ -102,6 +107,16 @@ nxs_sugg_get(const nxs_sugg_t *sg, unsigned i, const char **term, size_t *len, u
 	return true;
 }
 
+bool
+nxs_sugg_score(const nxs_sugg_t *sg, unsigned i, float *score)
+{
+	if (sg->kind != SUGG_DOC || i >= sg->count) {
+		return false;
+	}
+	if (score) *score = sg->items[i].score;
+	return true;
+}
+
 void
 nxs_sugg_release(nxs_sugg_t *sg)
 {
@@ -110,28 +125,38 @@ nxs_sugg_release(nxs_sugg_t *sg)
 
 /* {"token":"...","suggestions":[{"term":"...","distance":D,"df":N},...],"matches":M}; of a completion:
  * {"prefix":"...","completions":[{"term":"...","df":N},...],"matches":M}; of a wildcard match:
- * {"pattern":"...","terms":[{"term":"...","df":N},...],"matches":M} */
+ * {"pattern":"...","terms":[{"term":"...","df":N},...],"matches":M}; of a term vector:
+ * {"doc_id":N,"terms":[{"term":"...","tf":N,"df":N,"score":X},...],"matches":M} */
 char *
 nxs_sugg_tojson(nxs_sugg_t *sg, size_t *len)
 {
 	static const char *const head[] = { "{\"token\":", "{\"prefix\":", "{\"pattern\":" };
-	static const char *const list[] = { ",\"suggestions\":[", ",\"completions\":[", ",\"terms\":[" };
+	static const char *const list[] = { ",\"suggestions\":[", ",\"completions\":[", ",\"terms\":[", ",\"terms\":[" };
 	size_t cap = 96 + 6 * sg->token_len, o = 0;
 	char *s;
 
 	for (unsigned i = 0; i < sg->count; i++) {
-		cap += 64 + 6 * sg->items[i].len;
+		cap += 112 + 6 * sg->items[i].len;
 	}
 	if ((s = malloc(cap)) == NULL) {
 		return NULL;
 	}
-	o += (size_t)sprintf(s + o, "%s", head[sg->kind]);
-	o += json_str(s + o, sg->token, sg->token_len);
+	if (sg->kind == SUGG_DOC) {
+		o += (size_t)sprintf(s + o, "{\"doc_id\":%llu", (unsigned long long)sg->doc_id);
+	} else {
+		o += (size_t)sprintf(s + o, "%s", head[sg->kind]);
+		o += json_str(s + o, sg->token, sg->token_len);
+	}
 	o += (size_t)sprintf(s + o, "%s", list[sg->kind]);
 	for (unsigned i = 0; i < sg->count; i++) {
 		o += (size_t)sprintf(s + o, "%s{\"term\":", i ? "," : "");
 		o += json_str(s + o, sg->items[i].term, sg->items[i].len);
-		if (sg->kind != SUGG_SUGGEST) {
+		if (sg->kind == SUGG_DOC) {
+			o += (size_t)sprintf(s + o, ",\"tf\":%u,\"df\":%llu,\"score\":", sg->items[i].dist,
+			    (unsigned long long)sg->items[i].df);
+			o += fmt_real(s + o, (double)sg->items[i].score);
+			s[o++] = '}';
+		} else if (sg->kind != SUGG_SUGGEST) {
 			o += (size_t)sprintf(s + o, ",\"df\":%llu}", (unsigned long long)sg->items[i].df);
 		} else {
 			o += (size_t)sprintf(s + o, ",\"distance\":%u,\"df\":%llu}", sg->items[i].dist,
@@ -180,9 +205,10 @@ lookup_free(lookup_t *st)
 	free(st->matches);
 }
 
-/* what comes before the strings are looked at, and after the caller has read its params.  0 / -1 */
+/* what comes before the strings are looked at, and after the caller has read its params (bk: the call reads
+ * the BK image).  0 / -1 */
 static int
-lookup_enter(nxs_index_t *idx, const char *what, size_t n)
+lookup_enter(nxs_index_t *idx, const char *what, size_t n, bool bk)
 {
 	nxs_t *nxs = idx->nxs;
 
@@ -206,7 +232,7 @@ lookup_enter(nxs_index_t *idx, const char *what, size_t n)
 	/* new terms reach the BK image first.  (A batch whose fuzzy pass is still on the device reads the
 	 * image: it was synced for that pass, and nothing can have moved since without finishing the batch --
 	 * should the image be stale all the same, the pass is waited for before it is replaced.) */
-	if (idx->bk_upto != idx->last_id || idx->bk_flags_stale) {
+	if (bk && (idx->bk_upto != idx->last_id || idx->bk_flags_stale)) {
 		(void)late_finish(idx);
 		if (nxs_index_bk_sync(idx) == -1) {
 			return -1;
@@ -383,7 +409,7 @@ suggest_run(nxs_index_t *idx, nxs_params_t *params, const char *const *tokens, c
 
 	nxs_clear_error(nxs);
 	outs_clear(out, errs, n);
-	if (get_suggest_params(nxs, params, &k, &maxdist) == -1 || lookup_enter(idx, "suggest", n) == -1) {
+	if (get_suggest_params(nxs, params, &k, &maxdist) == -1 || lookup_enter(idx, "suggest", n, true) == -1) {
 		return -1;
 	}
 	/* the filters a query token goes through (tokenizer.c:205-227): normalizer, stop words, stemmer */
@@ -445,7 +471,7 @@ complete_run(nxs_index_t *idx, nxs_params_t *params, const char *const *prefixes
 
 	nxs_clear_error(nxs);
 	outs_clear(out, errs, n);
-	if (get_limit_param(nxs, params, "complete_limit", &k) == -1 || lookup_enter(idx, "complete", n) == -1) {
+	if (get_limit_param(nxs, params, "complete_limit", &k) == -1 || lookup_enter(idx, "complete", n, true) == -1) {
 		return -1;
 	}
 	/* a prefix is a fragment, not a word: the normalizer / lowercase stage only (nxs_filters_run_stages) */
@@ -517,7 +543,7 @@ wildcard_run(nxs_index_t *idx, nxs_params_t *params, const char *const *patterns
 
 	nxs_clear_error(nxs);
 	outs_clear(out, errs, n);
-	if (get_limit_param(nxs, params, "wildcard_limit", &k) == -1 || lookup_enter(idx, "wildcard", n) == -1) {
+	if (get_limit_param(nxs, params, "wildcard_limit", &k) == -1 || lookup_enter(idx, "wildcard", n, true) == -1) {
 		return -1;
 	}
 	/* every literal piece through the normalizer / lowercase stage only, runs of stars collapsed
@@ -582,6 +608,194 @@ nxs_index_wildcard(nxs_index_t *idx, nxs_params_t *params, const char *pattern, 
 	(void)wildcard_run(idx, params, &pattern, &len, 1, &sg, NULL);	/* (as nxs_index_suggest) */
 	return sg;
 }
+
+/* ---- term vectors (nxs_index_doc_terms) -------------------------------------------------- */
+
+/* `key`: a df floor (uint >= 1) */
+static int
+get_mindf_param(nxs_t *nxs, const nxs_params_t *params, const char *key, unsigned dflt, unsigned *mindf)
+{
+	uint64_t v;
+
+	*mindf = dflt;
+	if (params && nxs_params_get_uint(params, key, &v) == 0) {
+		if (v < 1 || v > UINT32_MAX) {
+			nxs_decl_err(nxs, NXS_ERR_INVALID, "invalid %s (>= 1)", key);
+			return -1;
+		}
+		*mindf = (unsigned)v;
+	}
+	return 0;
+}
+
+/* a term vector as the device reports it into an object; NULL: out of memory / an unknown term (declared) */
+static nxs_sugg_t *
+docterms_build(nxs_index_t *idx, uint64_t doc, uint64_t matches, unsigned count, const uint32_t *ids, const float *w,
+    const uint32_t *tf, const uint32_t *df, nxs_err_t *code)
+{
+	const uint8_t *terms[NXS_SUGGEST_MAX] = { NULL };
+	size_t tlens[NXS_SUGGEST_MAX] = { 0 };
+	unsigned dists[NXS_SUGGEST_MAX] = { 0 };
+	uint64_t dfs[NXS_SUGGEST_MAX] = { 0 };
+	nxs_sugg_t *sg;
+
+	for (unsigned j = 0; j < count; j++) {
+		if (ids[j] < 1 || ids[j] > idx->last_id) {
+			*code = NXS_ERR_FATAL;
+			nxs_decl_err(idx->nxs, *code, "the device named an unknown term for doc %llu", (unsigned long long)doc);
+			return NULL;
+		}
+		terms[j] = idx->terms[ids[j]].val;
+		tlens[j] = idx->terms[ids[j]].len;
+		dists[j] = tf[j];
+		dfs[j] = df[j];
+	}
+	if ((sg = sugg_build("", 0, false, matches, count, terms, tlens, dists, dfs)) == NULL) {
+		*code = NXS_ERR_SYSTEM;
+		nxs_decl_err(idx->nxs, *code, "out of memory");
+		return NULL;
+	}
+	sg->kind = SUGG_DOC;
+	sg->doc_id = doc;
+	for (unsigned j = 0; j < count; j++) {
+		sg->items[j].score = w[j];
+	}
+	return sg;
+}
+
+int
+docterms_rows(nxs_index_t *idx, int algo, const nxs_doc_id_t *docs, size_t n, unsigned mindf, unsigned k,
+    docterms_rows_t *r)
+{
+	const size_t m = n ? n : 1;
+
+	memset(r, 0, sizeof(*r));
+	r->ids = malloc(m * k * sizeof(*r->ids));
+	r->w = malloc(m * k * sizeof(*r->w));
+	r->tf = malloc(m * k * sizeof(*r->tf));
+	r->df = malloc(m * k * sizeof(*r->df));
+	r->counts = malloc(m * sizeof(*r->counts));
+	r->matches = malloc(m * sizeof(*r->matches));
+	r->found = malloc(m);
+	if (!r->ids || !r->w || !r->tf || !r->df || !r->counts || !r->matches || !r->found) {
+		nxs_decl_err(idx->nxs, NXS_ERR_SYSTEM, "out of memory");
+		docterms_rows_free(r);
+		return -1;
+	}
+	if (nxsgpu_doc_terms(idx->dev, algo, docs, (uint32_t)n, mindf, k, r->ids, r->w, r->tf, r->df, r->counts, r->matches,
+	    r->found) != 0) {
+		nxs_decl_err(idx->nxs, NXS_ERR_FATAL, "device doc_terms pass failed: %s", nxsgpu_last_error());
+		docterms_rows_free(r);
+		return -1;
+	}
+	for (size_t i = 0; i < n; i++) {
+		r->found[i] = r->found[i] && nxs_index_doc_live(idx, docs[i]);
+	}
+	return 0;
+}
+
+void
+docterms_rows_free(docterms_rows_t *r)
+{
+	free(r->ids);
+	free(r->w);
+	free(r->tf);
+	free(r->df);
+	free(r->counts);
+	free(r->matches);
+	free(r->found);
+	memset(r, 0, sizeof(*r));
+}
+
+int
+nxs_index_doc_terms_batch(nxs_index_t *idx, nxs_params_t *params, const nxs_doc_id_t *docs, size_t n,
+    nxs_sugg_t **out, nxs_err_t *errs)
+{
+	nxs_t *nxs = idx->nxs;
+	search_params_t sp;
+	docterms_rows_t r;
+	unsigned k, mindf;
+	int failed = 0;
+
+	nxs_clear_error(nxs);
+	outs_clear(out, errs, n);
+	if (get_limit_param(nxs, params, "docterms_limit", &k) == -1 ||
+	    get_mindf_param(nxs, params, "docterms_mindf", 1, &mindf) == -1 || get_search_params(idx, params, &sp) == -1 ||
+	    lookup_enter(idx, "doc_terms", n, false) == -1) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	if (docterms_rows(idx, sp.algo, docs, n, mindf, k, &r) == -1) {
+		return -1;
+	}
+	for (size_t i = 0; i < n; i++) {
+		nxs_err_t code = NXS_ERR_MISSING;
+
+		if (!r.found[i]) {
+			nxs_decl_err(nxs, code, "no such document");
+		} else {
+			out[i] = docterms_build(idx, docs[i], r.matches[i], r.counts[i] <= k ? r.counts[i] : k, r.ids + i * k,
+			    r.w + i * k, r.tf + i * k, r.df + i * k, &code);
+		}
+		if (!out[i]) {
+			if (errs) {
+				errs[i] = code;
+			}
+			failed++;
+		}
+	}
+	docterms_rows_free(&r);
+	return failed;
+}
+
+nxs_sugg_t *
+nxs_index_doc_terms(nxs_index_t *idx, nxs_params_t *params, nxs_doc_id_t doc)
+{
+	nxs_sugg_t *sg = NULL;
+
+	(void)nxs_index_doc_terms_batch(idx, params, &doc, 1, &sg, NULL);	/* (as nxs_index_suggest) */
+	return sg;
+}
+
+#ifdef NXS_TEST_HOOKS
+/* the parameters as nxs_index_doc_terms / nxs_index_similar read them: 0, or -1 with the error declared */
+int
+nxs_test_docterms_params(nxs_t *nxs, nxs_params_t *params, unsigned *k, unsigned *mindf, unsigned *similar_terms,
+    unsigned *similar_mindf, int *similar_self)
+{
+	nxs_index_t fake = { .nxs = nxs };
+	search_params_t sp;
+
+	nxs_clear_error(nxs);
+	if (get_limit_param(nxs, params, "docterms_limit", k) == -1 ||
+	    get_mindf_param(nxs, params, "docterms_mindf", 1, mindf) == -1 || get_search_params(&fake, params, &sp) == -1) {
+		return -1;
+	}
+	*similar_terms = sp.similar_terms;
+	*similar_mindf = sp.similar_mindf;
+	*similar_self = sp.similar_self;
+	return 0;
+}
+
+/* an nxs_sugg_t of the term-vector kind built by hand */
+nxs_sugg_t *
+nxs_test_docterms_build(uint64_t doc, uint64_t matches, unsigned count, const uint8_t *const *terms, const size_t *lens,
+    const unsigned *tfs, const uint64_t *dfs, const float *scores)
+{
+	nxs_sugg_t *sg = sugg_build("", 0, false, matches, count, terms, lens, tfs, dfs);
+
+	if (sg) {
+		sg->kind = SUGG_DOC;
+		sg->doc_id = doc;
+		for (unsigned i = 0; i < count; i++) {
+			sg->items[i].score = scores[i];
+		}
+	}
+	return sg;
+}
+#endif /* NXS_TEST_HOOKS */
 
 #ifdef NXS_TEST_HOOKS
 /* the parameters as nxs_index_wildcard / a search read them: 0, or -1 with the error declared */

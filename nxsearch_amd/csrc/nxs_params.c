@@ -550,6 +550,9 @@ get_search_params(nxs_index_t *idx, nxs_params_t *params, search_params_t *sp)
 	sp->wildcardmatch = false;
 	sp->wildcard_terms = 8;
 	sp->explain = false;
+	sp->similar_terms = 8;
+	sp->similar_mindf = 2;
+	sp->similar_self = false;
 	sp->algo = idx->algo;
 	if (!params) {
 		return 0;
@@ -592,6 +595,23 @@ get_search_params(nxs_index_t *idx, nxs_params_t *params, search_params_t *sp)
 			return -1;
 		}
 		sp->wildcard_terms = (unsigned)v;
+	}
+	if (nxs_params_get_uint(params, "similar_terms", &v) == 0) {
+		if (v < 1 || v > NXS_PREFIX_MAX) {
+			nxs_decl_err(idx->nxs, NXS_ERR_INVALID, "invalid similar_terms (1..%d)", NXS_PREFIX_MAX);
+			return -1;
+		}
+		sp->similar_terms = (unsigned)v;
+	}
+	if (nxs_params_get_uint(params, "similar_mindf", &v) == 0) {
+		if (v < 1 || v > UINT32_MAX) {
+			nxs_decl_err(idx->nxs, NXS_ERR_INVALID, "invalid similar_mindf (>= 1)");
+			return -1;
+		}
+		sp->similar_mindf = (unsigned)v;
+	}
+	if (nxs_params_get_bool(params, "similar_self", &fl) == 0 && fl) {
+		sp->similar_self = true;
 	}
 	return 0;
 }

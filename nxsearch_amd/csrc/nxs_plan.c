@@ -173,7 +173,8 @@ plan_cache_put(struct plan_cache *pc, const char *q, size_t n, bool fuzzy, const
 typedef struct {
 	const nxs_index_t *	idx;
 	const search_params_t *	sp;
-	const char *const *	queries;
+	const char *const *	queries;	/* or NULL: ... */
+	const nxs_doc_id_t *	docs;		/* ... the batch is nxs_index_similar's, query i is doc i's leaf */
 	qprep_t *		prep;
 	const struct plan_cache *pc;	/* read-only while the workers run */
 } plan_job_t;
@@ -186,6 +187,14 @@ plan_parse_chunk(void *arg, size_t lo, size_t hi)
 	for (size_t i = lo; i < hi; i++) {
 		qprep_t *q = &j->prep[i];
 
+		if (j->docs) {
+			nxs_query_prepare_doc(j->docs[i], q);
+			if (q->errcode) {
+				nxs_query_release_scratch(q);
+				q->compiled = true;
+			}
+			continue;
+		}
 		if (j->pc && !(j->sp->prefixmatch && strchr(j->queries[i], '*')) &&
 		    !(j->sp->wildcardmatch && strpbrk(j->queries[i], "*?"))) {
 			const pc_ent_t *e = plan_cache_find(j->pc, j->queries[i], strlen(j->queries[i]), j->sp->fuzzymatch);
@@ -374,18 +383,95 @@ out:
 	return ret;
 }
 
+/*
+ * The doc leaves of a batch (nxs_index_similar: every query is one): the batch's docs through ONE blocking
+ * nxsgpu_doc_terms pass with k = similar_terms and mindf = similar_mindf (the device answers a doc given twice
+ * once; docterms_rows, nxs_lookup.c).  A doc that is not live fails its query with NXS_ERR_MISSING.  (A doc
+ * shard never gets here: nxs_index_similar_batch refuses it.)
+ */
 static int
-plan_prefixes(nxs_index_t *idx, const search_params_t *sp, size_t n, qprep_t *prep)
+plan_resolve_docs(nxs_index_t *idx, const search_params_t *sp, size_t n, qprep_t *prep)
 {
-	if (plan_resolve(idx, n, prep, QPFX_PREFIX, sp->prefix_limit) == -1 ||
-	    plan_resolve(idx, n, prep, QPFX_WILD, sp->wildcard_terms) == -1) {
+	const unsigned k = sp->similar_terms;
+	size_t nd = 0, r = 0;
+	uint64_t *docs;
+	docterms_rows_t rows;
+	int ret = -1;
+
+	for (size_t i = 0; i < n; i++) {
+		nd += !prep[i].errcode && prep[i].n_pfx == 1 && prep[i].pfx[0].kind == QPFX_DOC;
+	}
+	if (!nd) {
+		return 0;
+	}
+	if ((docs = malloc(nd * sizeof(*docs))) == NULL) {
+		nxs_decl_err(idx->nxs, NXS_ERR_SYSTEM, "out of memory");
+		return -1;
+	}
+	for (size_t i = 0; i < n; i++) {
+		if (!prep[i].errcode && prep[i].n_pfx == 1 && prep[i].pfx[0].kind == QPFX_DOC) {
+			docs[r++] = strtoull(prep[i].pfx[0].val, NULL, 10);
+		}
+	}
+	if (docterms_rows(idx, sp->algo, docs, nd, sp->similar_mindf, k, &rows) == -1) {
+		free(docs);
+		return -1;
+	}
+	r = 0;
+	for (size_t i = 0; i < n; i++) {
+		qpfx_t *px;
+		const uint32_t *row;
+
+		if (prep[i].errcode || prep[i].n_pfx != 1 || prep[i].pfx[0].kind != QPFX_DOC) {
+			continue;
+		}
+		px = &prep[i].pfx[0];
+		row = rows.ids + r * k;
+		if (!rows.found[r]) {
+			prep[i].errcode = NXS_ERR_MISSING;
+			prep[i].errmsg = strdup("no such document");
+			r++;
+			continue;
+		}
+		px->n = rows.counts[r] <= k ? rows.counts[r] : k;
+		for (uint32_t e = 0; e < px->n; e++) {
+			if (row[e] < 1 || row[e] > idx->last_id) {
+				nxs_decl_err(idx->nxs, NXS_ERR_FATAL, "the device named an unknown term for a doc");
+				goto out;
+			}
+			px->ids[e] = row[e];
+			px->tval[e] = idx->terms[row[e]].val;
+			px->tlen[e] = idx->terms[row[e]].len;
+		}
+		r++;
+	}
+	ret = 0;
+out:
+	free(docs);
+	docterms_rows_free(&rows);
+	return ret;
+}
+
+static int
+plan_prefixes(nxs_index_t *idx, const search_params_t *sp, bool docs, size_t n, qprep_t *prep)
+{
+	if (docs ? plan_resolve_docs(idx, sp, n, prep) == -1 :
+	    (plan_resolve(idx, n, prep, QPFX_PREFIX, sp->prefix_limit) == -1 ||
+	    plan_resolve(idx, n, prep, QPFX_WILD, sp->wildcard_terms) == -1)) {
 		return -1;
 	}
 	for (size_t i = 0; i < n; i++) {
 		qprep_t *q = &prep[i];
 		bool miss = false;
 
-		if (q->errcode || !q->n_pfx) {
+		if (q->errcode) {
+			if (q->n_pfx && !q->compiled) {
+				nxs_query_release_scratch(q);	/* (a doc leaf whose doc is not live) */
+				q->compiled = true;
+			}
+			continue;
+		}
+		if (!q->n_pfx) {
 			continue;
 		}
 		if (nxs_query_splice(q) == -1) {
@@ -404,19 +490,20 @@ plan_prefixes(nxs_index_t *idx, const search_params_t *sp, size_t n, qprep_t *pr
 	return 0;
 }
 
-/* parse + lookups (+ compile for the queries without misses) on the worker threads; the misses into *fz */
+/* parse + lookups (+ compile for the queries without misses) on the worker threads; the misses into *fz.
+ * docs != NULL: queries is NULL, query i is the doc leaf of docs[i] (nxs_index_similar) */
 int
-plan_front(nxs_index_t *idx, const search_params_t *sp, const char *const *queries,
+plan_front(nxs_index_t *idx, const search_params_t *sp, const char *const *queries, const nxs_doc_id_t *docs,
     size_t n, qprep_t *prep, fz_set_t *fz)
 {
 	nxs_t *nxs = idx->nxs;
 	struct nxs_pool *pool = n >= 64 ? nxs_pool_get(nxs) : NULL;
-	plan_job_t job = { .idx = idx, .sp = sp, .queries = queries, .prep = prep, .pc = plan_cache_get(idx) };
+	plan_job_t job = { .idx = idx, .sp = sp, .queries = queries, .docs = docs, .prep = prep, .pc = plan_cache_get(idx) };
 	size_t n_fz = 0, fz_len = 0, k = 0, o = 0;
 
 	memset(fz, 0, sizeof(*fz));
 	pool_run(pool, plan_parse_chunk, &job, n, 16);
-	if ((sp->prefixmatch || sp->wildcardmatch) && plan_prefixes(idx, sp, n, prep) == -1) {
+	if ((docs || sp->prefixmatch || sp->wildcardmatch) && plan_prefixes(idx, sp, docs != NULL, n, prep) == -1) {
 		return -1;
 	}
 
@@ -489,20 +576,20 @@ plan_back(nxs_index_t *idx, const search_params_t *sp, const char *const *querie
 	 * still has to compile -- was put there by the first half's caller or is not cached) */
 	for (size_t i = 0; pc && i < n; i++) {
 		const qprep_t *q = &prep[i];
-		if (queries[i] && !q->cached && !q->errcode && !q->wide && !q->has_prefix) {
+		if (queries && queries[i] && !q->cached && !q->errcode && !q->wide && !q->has_prefix) {
 			plan_cache_put(pc, queries[i], strlen(queries[i]), sp->fuzzymatch, q);
 		}
 	}
 }
 
 int
-plan_batch(nxs_index_t *idx, const search_params_t *sp, const char *const *queries,
+plan_batch(nxs_index_t *idx, const search_params_t *sp, const char *const *queries, const nxs_doc_id_t *docs,
     size_t n, qprep_t *prep)
 {
 	fz_set_t fz;
 	int ret = -1;
 
-	if (plan_front(idx, sp, queries, n, prep, &fz) == -1) {
+	if (plan_front(idx, sp, queries, docs, n, prep, &fz) == -1) {
 		return -1;
 	}
 	if (fz.n) {
@@ -590,7 +677,7 @@ nxs_index_plan_batch(nxs_index_t *idx, nxs_params_t *params,
 		nxs_decl_err(idx->nxs, NXS_ERR_SYSTEM, "out of memory");
 		return -1;
 	}
-	if (plan_batch(idx, &sp, queries, n, prep) == -1) {
+	if (plan_batch(idx, &sp, queries, NULL, n, prep) == -1) {
 		failed = -1;
 	}
 	for (size_t i = 0; i < n; i++) {

@@ -711,6 +711,39 @@ nxs_query_prepare_wc(const nxs_index_t *idx, const char *query, bool prefixmatch
 	free(ff);
 }
 
+void
+nxs_query_prepare_doc(nxs_doc_id_t doc, qprep_t *out)
+{
+	qparse_t *pr = &out->parse;
+	qpfx_t *px;
+
+	memset(out, 0, sizeof(*out));
+	/* (a program of one leaf: the place nxs_query_splice puts the expansions in; its string is never read) */
+	nxs_query_parse("d", pr);
+	if (!pr->error && pr->n == 1 && pr->items[0].op == 0) {
+		out->tokens = arena_take(pr, 2 * sizeof(qtok_t));
+		out->pfx = calloc(1, sizeof(qpfx_t));
+	}
+	if (!out->tokens || !out->pfx) {
+		out->errcode = NXS_ERR_SYSTEM;
+		out->errmsg = strdup("out of memory");
+		return;
+	}
+	memset(out->tokens, 0, 2 * sizeof(qtok_t));
+	px = &out->pfx[0];
+	px->item = 0;
+	px->kind = QPFX_DOC;
+	if (asprintf(&px->val, "%llu", (unsigned long long)doc) == -1) {
+		px->val = NULL;
+		out->errcode = NXS_ERR_SYSTEM;
+		out->errmsg = strdup("out of memory");
+		return;
+	}
+	px->len = strlen(px->val);
+	out->n_pfx = 1;
+	out->has_prefix = true;
+}
+
 /*
  * The prefix leaves' expansions into the program and the token list: leaf i becomes e1 e2 OR e3 OR ... --
  * the postfix form of (e1 OR e2 OR ... OR em) -- and the token list is made again the way query_prepare

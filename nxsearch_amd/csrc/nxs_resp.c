@@ -97,7 +97,7 @@ nxs_resp_total(const nxs_resp_t *r, uint64_t *total)
  * fraction digit -- what yyjson's writer produces for results.c:158.  Pinned
  * by the reference only for 3.0 and 1.5 (t_misc.c:115-117).
  */
-static size_t
+size_t
 fmt_real(char *out, double v)
 {
 	char e[40], digs[24];
