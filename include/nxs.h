@@ -49,7 +49,8 @@ nxs_err_t	nxs_get_error(const nxs_t *, const char **);	/* nxs.h:48 */
 /* Parameters (nxs.h:54-67); the query path reads limit / algo / fuzzymatch / total / prefixmatch /
  * prefix_limit / explain / wildcardmatch / wildcard_terms, nxs_index_suggest reads suggest_limit /
  * suggest_maxdist, nxs_index_complete complete_limit, nxs_index_wildcard wildcard_limit, nxs_index_doc_terms
- * docterms_limit / docterms_mindf, nxs_index_similar similar_terms / similar_mindf / similar_self */
+ * docterms_limit / docterms_mindf, nxs_index_similar similar_terms / similar_mindf / similar_self,
+ * nxs_index_related related_limit / related_order / related_mindf / related_mincount / related_self */
 struct nxs_params;
 typedef struct nxs_params nxs_params_t;
 
@@ -339,6 +340,54 @@ bool		nxs_sugg_score(const nxs_sugg_t *, unsigned i, float *score);
 nxs_resp_t *	nxs_index_similar(nxs_index_t *, nxs_params_t *, nxs_doc_id_t doc);
 int		nxs_index_similar_batch(nxs_index_t *, nxs_params_t *, const nxs_doc_id_t *docs, size_t n,
 		    nxs_resp_t **resps, nxs_err_t *errs);
+
+/*
+ * Related terms (new; the reference has no call that starts from a result set): the dictionary terms that occur
+ * in a query's matches -- facet counts, "refine your search", tag clouds.
+ *
+ * DOC SET.  For a query string and params let M be the doc set of the query's expression: exactly what "total"
+ * counts -- live docs only, and empty under a ranking function that scores nothing.  The query is parsed,
+ * filtered and resolved as nxs_index_search would with the same params: "fuzzymatch", "prefixmatch" /
+ * "prefix_limit", "wildcardmatch" / "wildcard_terms" and "algo" are read as a search reads them; "limit", "total"
+ * and "explain" are ignored.  n = |M|.
+ *
+ * COUNTS.  For a dictionary term t, c(t) = the number of docs of M that hold t -- doc membership: a doc with tf
+ * 3 counts once --, df(t) = its live df (the rule of the suggestions).
+ *
+ * ELIGIBLE are the terms with c(t) >= "related_mincount" (uint >= 1, default 1), df(t) >= "related_mindf" (uint
+ * >= 1, default 1) that are not a term of the query's resolved token list -- what nxs_resp_tokens would report:
+ * tokens under a NOT and the expansions of prefix and wildcard leaves included.  "related_self" (bool, default
+ * false) set to true lifts that exclusion.
+ *
+ * ORDER.  "related_order" (string, default "count"); both values give a total order:
+ *   "count"  c descending, then term id ascending;
+ *   "share"  s descending as floats, then term id ascending, s(t) = the f32 nearest to the fp64 quotient
+ *            (double)c / (double)df.  c / df orders exactly as the lift (c / n) / (df / N) does, n and N being
+ *            constants of the query.  s >= 0 always.
+ * Any other string, or a uint out of range, fails the call with NXS_ERR_INVALID and a message that names the key.
+ *
+ * RESULT.  The first min(k, matches) eligible terms in that order, k = "related_limit" (uint,
+ * 1..NXS_SUGGEST_MAX, default 5), as a fifth kind of nxs_sugg_t: nxs_sugg_get reports the term's bytes,
+ * distance = c and df = the live df; nxs_sugg_score reports s, under either order; nxs_sugg_matches is the exact
+ * number of eligible terms; nxs_sugg_dropped is false; nxs_sugg_docs reports n (false on an object of the other
+ * calls).  nxs_sugg_tojson of such an object:
+ *   {"query":"<the string as given>","docs":n,"terms":[{"term":"...","count":c,"df":df,"score":s},...],"matches":M}
+ * the float as nxs_resp_tojson writes a score, strings with the escaping rules above.
+ *
+ * EDGE CASES.  n = 0, or a query that resolves to nothing: an empty list with docs 0 and matches 0, not an
+ * error.  A query of more than 32 live tokens (a search's wide plan) is refused with NXS_ERR_LIMIT "related is
+ * not available for a query of more than 32 terms"; a parse error is what a search reports for the string.  In a
+ * batch both are errs[i], and the batch goes on.  nxs_index_related_batch: as nxs_index_suggest_batch.
+ * Everything else is nxs_index_doc_terms': the call re-syncs with the files, is allowed with batches or a
+ * pending fuzzy pass in flight and neither reorders them nor changes their responses (a batch whose second half
+ * still waits for its fuzzy pass is sent on to the device first when this call's own tokens need that pass), is
+ * local under a communicator, and on a handle from nxs_index_open_shard fails with NXS_ERR_INVALID
+ * "related is not available on a doc shard".
+ */
+nxs_sugg_t *	nxs_index_related(nxs_index_t *, nxs_params_t *, const char *query, size_t len);
+int		nxs_index_related_batch(nxs_index_t *, nxs_params_t *, const char *const *queries, size_t n,
+		    nxs_sugg_t **out, nxs_err_t *errs);
+bool		nxs_sugg_docs(const nxs_sugg_t *, uint64_t *docs);
 
 /*
  * Batch entry point (new).  Runs `n` queries with one set of params as one

@@ -457,6 +457,45 @@ int		nxsgpu_doc_terms(nxsgpu_index_t *, int algo, const uint64_t *doc_ids, uint3
 void		nxsgpu_doc_terms_profile(nxsgpu_index_t *, double out[NXSGPU_DOCTERMS_PROF], int reset);
 
 /*
+ * ---- related terms of a query's matches -----------------------------------------------
+ *
+ * nxsgpu_related: for each of n plans the doc set M of the plan's expression -- exactly what nxsgpu_count counts:
+ * live docs, empty under a ranking function that scores nothing -- and the ELIGIBLE terms: c = the docs of M that
+ * hold the term (membership: a doc counts once whatever its tf) >= mincount, the live df (the length of the
+ * term's list, what nxsgpu_index_df reports) >= mindf, and, unless `self`, not one of the plan's own term_id[].
+ * order 0 ("count"): c descending, term id ascending; order 1 ("share"): s = (float)((double)c / (double)df)
+ * descending as floats, term id ascending (csrc/nxs_related.h).  Rows of k (1..NXSGPU_RELATED_MAX) entries:
+ * term_ids / count / df [n][k], counts[i] = min(k, matches[i]), matches[i] the exact number of eligible terms,
+ * docs[i] = |M|.  A plan that is empty or matches nothing has docs 0 and an empty row.  Identical plans are
+ * answered once and copied.  No impact is read: nothing is materialised.  0 / -1.
+ *
+ * A pass serves a group of G <= 32 distinct plans: k_rt_mask writes the doc sets as bits (a u32 per doc ordinal;
+ * k_count_tile's body with one more ending), k_rt_scan streams the posting array ONCE per group -- a workgroup per
+ * run of NXS_GPU_RELATED_RUN (default 4096; a multiple of 64, 64 at least) postings, a lane per posting gathers its
+ * doc's word, a wavefront that finds none set moves on, the others add one popcount per (segment of equal terms,
+ * plan bit) into c[g][term] --, k_rt_select keeps a top-k per part of a plan's count row (at most
+ * NXS_GPU_RELATED_PARTS, default 64, parts), k_rt_merge merges the parts.  The count rows of a group are bounded
+ * by NXS_GPU_RELATED_WS (default NXSGPU_RELATED_WS = 256 MiB: 32 rows of up to 2 M terms): G is what fits, one
+ * row at least, and a batch is cut into passes of G plans.  The pass has a stream, a grow-only workspace, pinned
+ * staging and events of its own: allowed while batches and fuzzy passes are in flight, takes none of their
+ * slots; blocking.  An index that is never asked allocates, uploads and launches nothing.  Under
+ * NXS_GPU_RELATED=host (the cross-check route) the posting array is copied back, the doc set is evaluated from
+ * the plan's postfix program on the host, the counts are taken by a plain loop and ranked by nxs_rt_rank.
+ *
+ * nxsgpu_related_profile: since the last reset -- out[0] distinct plans answered on the device, out[1] on the
+ * host, out[2] passes, out[3] / out[4] / out[5] / out[6] HIP-event ms of k_rt_mask / k_rt_scan / k_rt_select /
+ * k_rt_merge (with nxsgpu_set_profiling only), out[7] calls that had a plan to answer.
+ */
+#define	NXSGPU_RELATED_MAX	32
+#define	NXSGPU_RELATED_PROF	8
+#define	NXSGPU_RELATED_WS	(256ull << 20)
+int		nxsgpu_related(nxsgpu_index_t *, int algo, const nxsgpu_query_t *plans, uint32_t n, int order,
+		    uint32_t mindf, uint32_t mincount, int self, uint32_t k,
+		    uint32_t *term_ids, uint32_t *count, uint32_t *df,		/* rows [n][k] */
+		    uint32_t *counts, uint32_t *matches, uint32_t *docs);	/* [n] */
+void		nxsgpu_related_profile(nxsgpu_index_t *, double out[NXSGPU_RELATED_PROF], int reset);
+
+/*
  * ---- host batches as fixed-size records; query sharding over several GPUs ----
  *
  * The reference scales out by running independent worker processes

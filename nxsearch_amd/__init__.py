@@ -96,6 +96,7 @@ NXS_H_SYMBOLS = [
     "nxs_resp_tokens", "nxs_resp_token", "nxs_resp_explain",
     "nxs_index_doc_terms", "nxs_index_doc_terms_batch", "nxs_sugg_score",
     "nxs_index_similar", "nxs_index_similar_batch",
+    "nxs_index_related", "nxs_index_related_batch", "nxs_sugg_docs",
 ]
 # csrc/nxs_hooks.h: test hooks + bench accessors, only in builds with -DNXS_TEST_HOOKS (the default)
 NXS_HOOK_SYMBOLS = ["nxs_index_device", "nxs_index_host_profile", "nxs_index_shard_info", "nxs_test_pool", "nxs_test_assemble",
@@ -108,7 +109,9 @@ NXS_HOOK_SYMBOLS = ["nxs_index_device", "nxs_index_host_profile", "nxs_index_sha
                     "nxs_test_explain_params", "nxs_test_resp_build", "nxs_test_explain_search",
                     "nxs_test_explain_ordinal",
                     "nxs_test_docterms_params", "nxs_test_docterms_build", "nxs_test_docterms_lane",
-                    "nxs_test_docterms_key", "nxs_test_similar_drop"]
+                    "nxs_test_docterms_key", "nxs_test_similar_drop",
+                    "nxs_test_related_params", "nxs_test_related_build", "nxs_test_related_key",
+                    "nxs_test_related_share", "nxs_test_related_eligible", "nxs_test_related_rank"]
 NXS_GPU_H_SYMBOLS = [
     "nxsgpu_device_count", "nxsgpu_last_error", "nxsgpu_index_create",
     "nxsgpu_index_destroy", "nxsgpu_index_df", "nxsgpu_index_postings",
@@ -131,6 +134,7 @@ NXS_GPU_H_SYMBOLS = [
     "nxsgpu_wildcard", "nxsgpu_wildcard_profile",
     "nxsgpu_explain", "nxsgpu_explain_profile",
     "nxsgpu_doc_terms", "nxsgpu_doc_terms_profile",
+    "nxsgpu_related", "nxsgpu_related_profile",
 ]
 
 _lib = None
@@ -317,6 +321,35 @@ def lib():
         L.nxs_test_docterms_key.argtypes = [C.c_float, C.c_uint32]
         L.nxs_test_similar_drop.restype = None
         L.nxs_test_similar_drop.argtypes = [vp, C.c_uint64, C.c_uint64]
+    L.nxs_index_related.restype = vp
+    L.nxs_index_related.argtypes = [vp, vp, C.c_char_p, C.c_size_t]
+    L.nxs_index_related_batch.restype = C.c_int
+    L.nxs_index_related_batch.argtypes = [vp, vp, C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(vp), C.POINTER(C.c_int)]
+    L.nxs_sugg_docs.restype = C.c_bool
+    L.nxs_sugg_docs.argtypes = [vp, C.POINTER(C.c_uint64)]
+    u32p = C.POINTER(C.c_uint32)
+    L.nxsgpu_related.restype = C.c_int
+    L.nxsgpu_related.argtypes = [vp, C.c_int, C.POINTER(GpuQuery), C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_int,
+                                 C.c_uint32, u32p, u32p, u32p, u32p, u32p, u32p]
+    L.nxsgpu_related_profile.restype = None
+    L.nxsgpu_related_profile.argtypes = [vp, C.POINTER(C.c_double), C.c_int]
+    if hasattr(L, "nxs_test_related_params"):
+        L.nxs_test_related_params.restype = C.c_int
+        L.nxs_test_related_params.argtypes = [vp, vp, C.POINTER(C.c_uint), C.POINTER(C.c_int), C.POINTER(C.c_uint),
+                                              C.POINTER(C.c_uint), C.POINTER(C.c_int)]
+        L.nxs_test_related_build.restype = vp
+        L.nxs_test_related_build.argtypes = [C.c_char_p, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint,
+                                             C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(C.c_uint),
+                                             C.POINTER(C.c_uint64)]
+        L.nxs_test_related_key.restype = C.c_uint64
+        L.nxs_test_related_key.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32]
+        L.nxs_test_related_share.restype = C.c_float
+        L.nxs_test_related_share.argtypes = [C.c_uint32, C.c_uint32]
+        L.nxs_test_related_eligible.restype = C.c_bool
+        L.nxs_test_related_eligible.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u32p, C.c_uint32]
+        L.nxs_test_related_rank.restype = C.c_int
+        L.nxs_test_related_rank.argtypes = [C.c_int, u32p, u32p, C.c_uint32, C.c_uint32, C.c_uint32, u32p, C.c_uint32,
+                                            C.c_uint32, u32p, C.POINTER(C.c_uint64)]
     L.nxsgpu_wildcard_profile.restype = None
     L.nxsgpu_wildcard_profile.argtypes = [vp, C.POINTER(C.c_double), C.c_int]
     L.nxsgpu_explain_profile.restype = None
@@ -628,6 +661,36 @@ def _drain_docterms(sg, json=False):
             i += 1
         assert i == L.nxs_sugg_count(sg) and not L.nxs_sugg_dropped(sg)
         out.matches = L.nxs_sugg_matches(sg)
+        return out
+    finally:
+        L.nxs_sugg_release(sg)
+
+
+class Related(list):
+    """The related terms of one query (nxs_sugg_t of nxs_index_related): [(term: bytes, count, df, score), ...]
+    best first, with `.matches` = the exact number of eligible terms and `.docs` = the size of the query's doc
+    set."""
+    matches = 0
+    docs = 0
+
+
+def _drain_related(sg, json=False):
+    """nxs_sugg_t of the related kind -> Related (or its JSON text); releases the object"""
+    L = lib()
+    try:
+        if json:
+            n = C.c_size_t()
+            return _take(L.nxs_sugg_tojson(sg, C.byref(n)))
+        out = Related()
+        term, ln, c, df, sc, docs = C.c_void_p(), C.c_size_t(), C.c_uint(), C.c_uint64(), C.c_float(), C.c_uint64()
+        i = 0
+        while L.nxs_sugg_get(sg, i, C.byref(term), C.byref(ln), C.byref(c), C.byref(df)):
+            assert L.nxs_sugg_score(sg, i, C.byref(sc))
+            out.append((C.string_at(term.value, ln.value), c.value, df.value, sc.value))
+            i += 1
+        assert i == L.nxs_sugg_count(sg) and not L.nxs_sugg_dropped(sg) and L.nxs_sugg_docs(sg, C.byref(docs))
+        out.matches = L.nxs_sugg_matches(sg)
+        out.docs = docs.value
         return out
     finally:
         L.nxs_sugg_release(sg)
@@ -1099,6 +1162,47 @@ class Index:
         lib().nxsgpu_doc_terms_profile(self.device, out, 1 if reset else 0)
         return {"calls": int(out[0]), "ord_ms": out[1], "scan_ms": out[2], "merge_ms": out[3], "passes": int(out[4]),
                 "device_docs": int(out[5]), "host_docs": int(out[6]), "eligible": int(out[7])}
+
+    def related(self, queries, limit=None, order=None, mindf=None, mincount=None, include_self=None, fuzzymatch=None,
+                prefixmatch=None, wildcardmatch=None, algo=None, json=False):
+        """nxs_index_related_batch(): for every query string the dictionary terms that occur in the docs the
+        query matches, with count = the matching docs that hold the term and the live df, best `limit` (1..32,
+        default 5) by `order` -- "count" (the default): count descending, or "share": count / df descending --
+        then term id; terms with count < `mincount` or df < `mindf` (default 1 each) and, unless `include_self`,
+        the query's own resolved terms are left out -> a list of Related, one per query, entries (term, count,
+        df, score = count / df), `.matches` exact, `.docs` the number of matching docs (an NxsError instance
+        in the slot of a query that failed: a parse error, more than 32 terms); json: their JSON texts."""
+        L = lib()
+        n = len(queries)
+        p = _make_params(None, algo, fuzzymatch, False, prefixmatch, None, False, wildcardmatch, None)
+        if any(v is not None for v in (limit, order, mindf, mincount, include_self)):
+            p = p or L.nxs_params_create()
+            for key, v in ((b"related_limit", limit), (b"related_mindf", mindf), (b"related_mincount", mincount)):
+                if v is not None:
+                    L.nxs_params_set_uint(p, key, v)
+            if order is not None:
+                L.nxs_params_set_str(p, b"related_order", _b(order))
+            if include_self is not None:
+                L.nxs_params_set_bool(p, b"related_self", bool(include_self))
+        out = (C.c_void_p * max(n, 1))()
+        errs = (C.c_int * max(n, 1))()
+        qs = (C.c_char_p * max(n, 1))(*[_b(q) for q in queries])
+        try:
+            r = L.nxs_index_related_batch(self._h, p, qs, n, out, errs)
+        finally:
+            if p:
+                L.nxs_params_release(p)
+        if r < 0:
+            self.nxs._raise()
+        return [_drain_related(out[i], json) if out[i] else NxsError(errs[i], "query %d failed" % i) for i in range(n)]
+
+    def related_profile(self, reset=False):
+        """nxsgpu_related_profile(): distinct plans answered on the device / on the host, passes, HIP-event ms per
+        kernel (profiling on), calls that had a plan to answer."""
+        out = (C.c_double * 8)()
+        lib().nxsgpu_related_profile(self.device, out, 1 if reset else 0)
+        return {"device_queries": int(out[0]), "host_queries": int(out[1]), "passes": int(out[2]), "mask_ms": out[3],
+                "scan_ms": out[4], "select_ms": out[5], "merge_ms": out[6], "calls": int(out[7])}
 
     def explain_profile(self, reset=False):
         """nxsgpu_explain_profile(): explain passes, HIP-event ms of k_explain (profiling on), (result, token)

@@ -7,7 +7,7 @@
  *   nxs_resp.c      response object: slab, accessors, JSON, explanations
  *   nxs_plan.c      plan cache and the front half of a batch (parse, lookups, prefixes, misses, compile)
  *   nxs_batch.c     begin / end, the late second half, exact fix-up and its protocol, query sharding
- *   nxs_lookup.c    nxs_sugg_t, suggest, complete
+ *   nxs_lookup.c    nxs_sugg_t, suggest, complete, wildcard, doc_terms, related
  *   nxs_docshard.c  doc-sharded collections: search, attach, refresh
  *   nxs_hooks.c     the test hooks that reach no static
  *
@@ -21,6 +21,7 @@
 #include <time.h>
 
 #include "nxs_impl.h"
+#include "nxs_related.h"
 
 #pragma GCC visibility push(hidden)
 
@@ -65,6 +66,17 @@ typedef struct {
 
 int	get_ranking_func_id(const char *name);
 int	get_search_params(nxs_index_t *, nxs_params_t *, search_params_t *);
+
+/* nxs_index_related's own keys (the query is read with a search's: search_params_t) */
+typedef struct {
+	unsigned	k;		/* "related_limit": terms returned (1..NXS_SUGGEST_MAX, default 5) */
+	int		order;		/* "related_order": NXS_RT_COUNT ("count", the default) / NXS_RT_SHARE ("share") */
+	unsigned	mindf;		/* "related_mindf": the df floor (>= 1, default 1) */
+	unsigned	mincount;	/* "related_mincount": the floor of c (>= 1, default 1) */
+	bool		self;		/* "related_self": the query's own terms stay eligible */
+} related_params_t;
+
+int	get_related_params(nxs_t *, const nxs_params_t *, related_params_t *);
 
 /* ---- nxs_resp.c ----------------------------------------------------------------------- */
 

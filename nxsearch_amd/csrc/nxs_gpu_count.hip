@@ -22,137 +22,13 @@
 #include "nxs_gpu_int.h"
 #include "nxs_gpu_dev.h"
 
-#define	CNT_THREADS	256
-#define	CNT_TILE_WORDS	4096				/* 16 KB of LDS: ten workgroups per CU */
-#define	CNT_TILE8_DOCS	(CNT_TILE_WORDS * 4)		/* byte masks */
-#define	CNT_TILE32_DOCS	CNT_TILE_WORDS			/* word masks */
 #define	CNT_REQ_CHUNK	2048				/* driver postings per workgroup */
 
-struct count_q_t {
-	uint32_t	nt, prog_len;
-	uint32_t	tok_base;	/* into tok: nt x (pbeg, pend) */
-	uint32_t	prog_base;	/* into prog (nt > 8) */
-	uint32_t	truth[8];	/* nt <= 8 */
-	uint32_t	req;		/* tokens present in every matching mask */
-	uint32_t	driver;		/* k_count_req: the shortest required token */
-	uint32_t	out;		/* index into totals */
-	uint32_t	pad;
-};
-struct count_item_t { uint32_t q, r; };
-
-struct count_args_t {
-	const uint64_t *	post_dt;
-	const count_q_t *	q;
-	const uint64_t *	tok;
-	const uint8_t *		prog;
-	const count_item_t *	items;
-	uint64_t		n_docs;
-	uint32_t *		totals;
-};
-
-/* first position in dt[lo, hi) whose doc ordinal is >= doc */
-__device__ static inline uint64_t
-dt_lower_bound(const uint64_t *__restrict__ dt, uint64_t lo, uint64_t hi, uint64_t doc)
-{
-	while (lo < hi) {
-		const uint64_t mid = lo + ((hi - lo) >> 1);
-		if ((dt[mid] >> 32) < doc) lo = mid + 1; else hi = mid;
-	}
-	return lo;
-}
-
+/* (the tile's body -- count_q_t, count_args_t, count_tile_body -- is nxs_gpu_dev.h's: k_rt_mask shares it) */
 __global__ void __launch_bounds__(CNT_THREADS)
 k_count_tile(const count_args_t A)
 {
-	__shared__ uint32_t s_tile[CNT_TILE_WORDS];
-	__shared__ uint64_t s_lo[NXSGPU_MAX_TOKENS], s_hi[NXSGPU_MAX_TOKENS];
-	__shared__ uint32_t s_truth[8];
-	__shared__ uint8_t s_prog[NXSGPU_MAX_PROG];
-	__shared__ uint32_t s_any, s_cnt;
-
-	const unsigned tid = threadIdx.x;
-	const count_item_t it = A.items[blockIdx.x];
-	const count_q_t Q = A.q[it.q];
-	const uint64_t *__restrict__ dt = A.post_dt;
-	const bool bytes = Q.nt <= 8;
-	const uint32_t W = bytes ? CNT_TILE8_DOCS : CNT_TILE32_DOCS;
-	const uint64_t d_lo = (uint64_t)it.r * W;
-	const uint64_t d_hi = min(d_lo + W, A.n_docs);
-
-	if (tid == 0) {
-		s_any = 0;
-		s_cnt = 0;
-	}
-	__syncthreads();
-	/* the range's boundaries in every token's list (two slots naming one term: each its own) */
-	if (tid < Q.nt) {
-		const uint64_t pb = A.tok[Q.tok_base + 2 * tid], pe = A.tok[Q.tok_base + 2 * tid + 1];
-		const uint64_t lo = dt_lower_bound(dt, pb, pe, d_lo);
-		const uint64_t hi = (d_hi >= A.n_docs) ? pe : dt_lower_bound(dt, lo, pe, d_hi);
-		s_lo[tid] = lo;
-		s_hi[tid] = hi;
-		if (hi > lo) {
-			atomicOr(&s_any, 1u);
-		}
-	}
-	__syncthreads();
-	if (!s_any) {
-		return;		/* no token has a posting here: no tile work */
-	}
-	for (uint32_t i = tid; i < CNT_TILE_WORDS; i += CNT_THREADS) {
-		s_tile[i] = 0;
-	}
-	if (bytes) {
-		if (tid < 8) {
-			s_truth[tid] = Q.truth[tid];
-		}
-	} else {
-		for (uint32_t i = tid; i < Q.prog_len; i += CNT_THREADS) {
-			s_prog[i] = A.prog[Q.prog_base + i];
-		}
-	}
-	__syncthreads();
-	for (uint32_t t = 0; t < Q.nt; t++) {
-		const uint64_t hi = s_hi[t];
-		for (uint64_t i = s_lo[t] + tid; i < hi; i += CNT_THREADS) {
-			const uint32_t d = (uint32_t)((dt[i] >> 32) - d_lo);
-			if (d < W) {
-				if (bytes) {
-					atomicOr(&s_tile[d >> 2], (1u << t) << ((d & 3) * 8));
-				} else {
-					atomicOr(&s_tile[d], 1u << t);
-				}
-			}
-		}
-	}
-	__syncthreads();
-
-	/* (docs beyond the range's end have no posting: their masks are zero) */
-	const uint32_t nd = (uint32_t)(d_hi - d_lo);
-	const uint32_t words = bytes ? (nd + 3) / 4 : nd;
-	uint32_t n = 0;		/* wavefront-uniform */
-	for (uint32_t base = 0; base < words; base += CNT_THREADS) {
-		const uint32_t w = base + tid;
-		const uint32_t word = w < words ? s_tile[w] : 0u;
-		if (bytes) {
-#pragma unroll
-			for (int j = 0; j < 4; j++) {
-				const uint32_t m = (word >> (8 * j)) & 0xffu;
-				const bool match = m != 0 && ((s_truth[m >> 5] >> (m & 31)) & 1u);
-				n += (uint32_t)__popcll(ballot64(match));
-			}
-		} else {
-			const bool match = word != 0 && eval_prog(s_prog, Q.prog_len, word);
-			n += (uint32_t)__popcll(ballot64(match));
-		}
-	}
-	if ((tid & (WAVE - 1)) == 0 && n) {
-		atomicAdd(&s_cnt, n);
-	}
-	__syncthreads();
-	if (tid == 0 && s_cnt) {
-		atomicAdd(&A.totals[Q.out], s_cnt);
-	}
+	count_tile_body<false>(A);
 }
 
 __global__ void __launch_bounds__(CNT_THREADS)
@@ -486,6 +362,7 @@ count_launch(nxsgpu_index_t *ix, count_buf_t &cb, uint32_t *d_totals, hipStream_
 	a.prog = D.prog;
 	a.n_docs = ix->n_docs;
 	a.totals = d_totals ? d_totals : D.totals;
+	a.mask = NULL;
 	cb.timed = false;
 	if (ix->profiling) {
 		bool ok = true;

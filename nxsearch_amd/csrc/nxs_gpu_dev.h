@@ -1,7 +1,9 @@
 /*
  * nxs_gpu_dev.h -- device-side helpers shared by the scan / replay kernels:
  * threshold hand-down between the wavefronts of a query, wave-level predicates
- * as scalar masks, the AGPR-held prefetch windows, 64-ary searches.
+ * as scalar masks, the AGPR-held prefetch windows, 64-ary searches; the doc-range
+ * tile of the count and related-terms mask kernels (count_tile_body) and the
+ * per-workgroup running top-k of u64 keys (group_topk_take / group_topk_merge).
  */
 #ifndef NXS_GPU_DEV_H
 #define NXS_GPU_DEV_H
@@ -578,6 +580,262 @@ bigk_publish(const scan_args_t &A, uint64_t seg, const uint32_t *hist, uint32_t 
 			__hip_atomic_store(A.pub_sk + seg * 8 + j, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 		}
 	}
+}
+
+/*
+ * ---- a doc range's presence masks in an LDS tile: the count pass (k_count_tile, nxs_gpu_count.hip) and the doc
+ * set of the related-terms pass (k_rt_mask, nxs_gpu_related.hip) ----
+ *
+ * One workgroup per (query, doc range): the range's presence masks (bytes up to 8 tokens, words up to 32) are
+ * filled by LDS atomics from the tokens' posting ranges and evaluated by truth table / postfix program.  The
+ * matches are counted by ballot, one global atomicAdd into totals[Q.out] per workgroup at most.  MASK: bit Q.out
+ * of mask[doc ordinal] is set for every match as well -- the doc set as a set (Q.out < 32 then; the words are
+ * shared by the queries of a group, hence the atomic OR).
+ */
+#define	CNT_THREADS	256
+#define	CNT_TILE_WORDS	4096				/* 16 KB of LDS: ten workgroups per CU */
+#define	CNT_TILE8_DOCS	(CNT_TILE_WORDS * 4)		/* byte masks */
+#define	CNT_TILE32_DOCS	CNT_TILE_WORDS			/* word masks */
+
+struct count_q_t {
+	uint32_t	nt, prog_len;
+	uint32_t	tok_base;	/* into tok: nt x (pbeg, pend) */
+	uint32_t	prog_base;	/* into prog (nt > 8) */
+	uint32_t	truth[8];	/* nt <= 8 */
+	uint32_t	req;		/* tokens present in every matching mask */
+	uint32_t	driver;		/* k_count_req: the shortest required token */
+	uint32_t	out;		/* index into totals */
+	uint32_t	pad;
+};
+struct count_item_t { uint32_t q, r; };
+
+struct count_args_t {
+	const uint64_t *	post_dt;
+	const count_q_t *	q;
+	const uint64_t *	tok;
+	const uint8_t *		prog;
+	const count_item_t *	items;
+	uint64_t		n_docs;
+	uint32_t *		totals;
+	uint32_t *		mask;		/* k_rt_mask only: [n_docs] */
+};
+
+/* first position in dt[lo, hi) whose doc ordinal is >= doc */
+__device__ static inline uint64_t
+dt_lower_bound(const uint64_t *__restrict__ dt, uint64_t lo, uint64_t hi, uint64_t doc)
+{
+	while (lo < hi) {
+		const uint64_t mid = lo + ((hi - lo) >> 1);
+		if ((dt[mid] >> 32) < doc) lo = mid + 1; else hi = mid;
+	}
+	return lo;
+}
+
+template <bool MASK>
+__device__ __forceinline__ void
+count_tile_body(const count_args_t &A)
+{
+	__shared__ uint32_t s_tile[CNT_TILE_WORDS];
+	__shared__ uint64_t s_lo[NXSGPU_MAX_TOKENS], s_hi[NXSGPU_MAX_TOKENS];
+	__shared__ uint32_t s_truth[8];
+	__shared__ uint8_t s_prog[NXSGPU_MAX_PROG];
+	__shared__ uint32_t s_any, s_cnt;
+
+	const unsigned tid = threadIdx.x;
+	const count_item_t it = A.items[blockIdx.x];
+	const count_q_t Q = A.q[it.q];
+	const uint64_t *__restrict__ dt = A.post_dt;
+	const bool bytes = Q.nt <= 8;
+	const uint32_t W = bytes ? CNT_TILE8_DOCS : CNT_TILE32_DOCS;
+	const uint64_t d_lo = (uint64_t)it.r * W;
+	const uint64_t d_hi = min(d_lo + W, A.n_docs);
+
+	if (tid == 0) {
+		s_any = 0;
+		s_cnt = 0;
+	}
+	__syncthreads();
+	/* the range's boundaries in every token's list (two slots naming one term: each its own) */
+	if (tid < Q.nt) {
+		const uint64_t pb = A.tok[Q.tok_base + 2 * tid], pe = A.tok[Q.tok_base + 2 * tid + 1];
+		const uint64_t lo = dt_lower_bound(dt, pb, pe, d_lo);
+		const uint64_t hi = (d_hi >= A.n_docs) ? pe : dt_lower_bound(dt, lo, pe, d_hi);
+		s_lo[tid] = lo;
+		s_hi[tid] = hi;
+		if (hi > lo) {
+			atomicOr(&s_any, 1u);
+		}
+	}
+	__syncthreads();
+	if (!s_any) {
+		return;		/* no token has a posting here: no tile work */
+	}
+	for (uint32_t i = tid; i < CNT_TILE_WORDS; i += CNT_THREADS) {
+		s_tile[i] = 0;
+	}
+	if (bytes) {
+		if (tid < 8) {
+			s_truth[tid] = Q.truth[tid];
+		}
+	} else {
+		for (uint32_t i = tid; i < Q.prog_len; i += CNT_THREADS) {
+			s_prog[i] = A.prog[Q.prog_base + i];
+		}
+	}
+	__syncthreads();
+	for (uint32_t t = 0; t < Q.nt; t++) {
+		const uint64_t hi = s_hi[t];
+		for (uint64_t i = s_lo[t] + tid; i < hi; i += CNT_THREADS) {
+			const uint32_t d = (uint32_t)((dt[i] >> 32) - d_lo);
+			if (d < W) {
+				if (bytes) {
+					atomicOr(&s_tile[d >> 2], (1u << t) << ((d & 3) * 8));
+				} else {
+					atomicOr(&s_tile[d], 1u << t);
+				}
+			}
+		}
+	}
+	__syncthreads();
+
+	/* (docs beyond the range's end have no posting: their masks are zero) */
+	const uint32_t nd = (uint32_t)(d_hi - d_lo);
+	const uint32_t words = bytes ? (nd + 3) / 4 : nd;
+	uint32_t n = 0;		/* wavefront-uniform */
+	for (uint32_t base = 0; base < words; base += CNT_THREADS) {
+		const uint32_t w = base + tid;
+		const uint32_t word = w < words ? s_tile[w] : 0u;
+		if (bytes) {
+#pragma unroll
+			for (int j = 0; j < 4; j++) {
+				const uint32_t m = (word >> (8 * j)) & 0xffu;
+				const bool match = m != 0 && ((s_truth[m >> 5] >> (m & 31)) & 1u);
+				n += (uint32_t)__popcll(ballot64(match));
+				if constexpr (MASK) {
+					if (match && 4 * w + j < nd) {
+						atomicOr(&A.mask[d_lo + 4 * w + j], 1u << (Q.out & 31));
+					}
+				}
+			}
+		} else {
+			const bool match = word != 0 && eval_prog(s_prog, Q.prog_len, word);
+			n += (uint32_t)__popcll(ballot64(match));
+			if constexpr (MASK) {
+				if (match && w < nd) {
+					atomicOr(&A.mask[d_lo + w], 1u << (Q.out & 31));
+				}
+			}
+		}
+	}
+	if ((tid & (WAVE - 1)) == 0 && n) {
+		atomicAdd(&s_cnt, n);
+	}
+	__syncthreads();
+	if (tid == 0 && s_cnt) {
+		atomicAdd(&A.totals[Q.out], s_cnt);
+	}
+}
+
+/*
+ * ---- a running top-k of u64 keys per workgroup (k_wc_match / k_wc_merge, k_rt_select / k_rt_merge) ----
+ *
+ * Keys are distinct, never 0 and never ~0 (the padding); ascending keys are the order wanted.
+ */
+
+/* the group-wide minimum of `best` (s_w: one slot per wavefront; two barriers) */
+template <int GROUP>
+static __device__ __forceinline__ uint64_t
+group_min_u64(uint64_t best, uint64_t *s_w, unsigned tid)
+{
+	for (int o = 32; o; o >>= 1) {
+		const uint64_t c = (uint64_t)__shfl_xor((long long)best, o);
+		if (c < best) {
+			best = c;
+		}
+	}
+	if ((tid & 63) == 0) {
+		s_w[tid >> 6] = best;
+	}
+	__syncthreads();
+	best = s_w[0];
+	for (unsigned w = 1; w < GROUP / WAVE; w++) {
+		if (s_w[w] < best) {
+			best = s_w[w];
+		}
+	}
+	__syncthreads();
+	return best;
+}
+
+/*
+ * s_top[0 .. k) (LDS, ascending, padded with ~0) takes a tile's keys -- `mine`, ~0 = none: k rounds of a
+ * group-wide minimum over {kept keys} + {the tile's keys}.  Round r delivers the r-th smallest key of the union:
+ * the smallest above round r - 1's.  The kept keys sit in registers of threads 0 .. k - 1, so s_top can be
+ * rewritten as the rounds go.  Called by the whole workgroup after a barrier; k <= GROUP.
+ */
+template <int GROUP>
+static __device__ __forceinline__ void
+group_topk_take(uint64_t mine, uint64_t *s_top, uint32_t k, uint64_t *s_w, unsigned tid)
+{
+	const uint64_t none = ~0ull;
+	const uint64_t kept = tid < k ? s_top[tid] : none;
+	uint64_t prev = 0;
+
+	for (uint32_t r = 0; r < k; r++) {
+		uint64_t best = none;
+
+		if (mine > prev) {
+			best = mine;
+		}
+		if (kept > prev && kept < best) {
+			best = kept;
+		}
+		best = group_min_u64<GROUP>(best, s_w, tid);
+		if (best == none) {
+			break;		/* (fewer than k so far: the slots from r on were ~0 already) */
+		}
+		if (tid == 0) {
+			s_top[r] = best;
+		}
+		prev = best;
+	}
+}
+
+/* the k smallest of list[0 .. n), in order: emit(r, key) runs on thread 0 for the r-th; -> how many there are */
+template <int GROUP, typename F>
+static __device__ __forceinline__ uint32_t
+group_topk_merge(const uint64_t *__restrict__ list, uint32_t n, uint32_t k, uint64_t *s_w, unsigned tid, F &&emit)
+{
+	const uint64_t none = ~0ull;
+	uint64_t mine = none, prev = 0;
+	uint32_t nout = 0;
+
+	if (tid < n) {
+		mine = list[tid];
+	}
+	for (uint32_t r = 0; r < k; r++) {
+		uint64_t best = none;
+
+		if (mine > prev) {
+			best = mine;
+		}
+		for (uint32_t i = tid + GROUP; i < n; i += GROUP) {
+			const uint64_t c = list[i];
+			if (c > prev && c < best) {
+				best = c;
+			}
+		}
+		best = group_min_u64<GROUP>(best, s_w, tid);
+		if (best == none) {
+			break;
+		}
+		if (tid == 0) {
+			emit(r, best);
+		}
+		prev = best;
+		nout++;
+	}
+	return nout;
 }
 
 #endif /* NXS_GPU_DEV_H */

@@ -142,6 +142,13 @@ cfg_from_env(gpu_cfg_t &c)
 	}
 	c.docterms_parts = (uint32_t)u64("NXS_GPU_DOCTERMS_PARTS", 512, 1, 4096);
 	c.docterms_ws = u64("NXS_GPU_DOCTERMS_WS", 64ull << 20, 1, 1ull << 32);
+	{
+		const char *e = getenv("NXS_GPU_RELATED");
+		c.related_host = e && !strcmp(e, "host");
+	}
+	c.related_run = (uint32_t)u64("NXS_GPU_RELATED_RUN", 4096, 64, 1u << 20);
+	c.related_parts = (uint32_t)u64("NXS_GPU_RELATED_PARTS", 64, 1, 1024);
+	c.related_ws = u64("NXS_GPU_RELATED_WS", NXSGPU_RELATED_WS, 1, 1ull << 34);
 }
 
 /* ------------------------------------------------------------------ */
@@ -673,6 +680,7 @@ nxsgpu_index_destroy(nxsgpu_index_t *ix)
 	px_free(ix);
 	ex_free(ix);
 	dv_free(ix);
+	rt_free(ix);
 	bk_aux_free(ix);
 	(void)hipFree(ix->ws);
 	(void)hipFree(ix->fz);

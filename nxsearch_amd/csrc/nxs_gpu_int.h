@@ -36,6 +36,9 @@
  *                         token added to the score, looked up in the CSR (nxs_explain.h)
  *  nxs_gpu_docterms.hip   term vectors of docs: every term's list asked for a chunk of docs (k_dv_scan, nxs_docterms.h),
  *                         a running top-k per doc and part, the parts merged (k_dv_merge)
+ *  nxs_gpu_related.hip    related terms of a query's matches: the doc sets of a group of plans as bits (k_rt_mask: k_count_tile's
+ *                         body), one pass over the posting array that meets every list with them (k_rt_scan), a top-k
+ *                         per plan and part (k_rt_select), the parts merged (k_rt_merge); nxs_related.h
  *  nxs_gpu_plan.hip       host only: query classes, the work list (build_worklist) and
  *                         the layout of a batch's arrays (batch_layout)
  *  nxs_gpu_search.hip     kernel dispatch, blocking search, batches in flight
@@ -195,6 +198,14 @@ struct gpu_cfg_t {
 					 * each per chunk of 64 docs (k_dv_scan); its partial top-k lists are [docs][parts][k] keys */
 	uint64_t	docterms_ws;	/* NXS_GPU_DOCTERMS_WS (64 MiB): bytes of partial lists per pass; a larger batch is cut into passes
 					 * of whole chunks (one chunk at least) */
+	bool		related_host;	/* NXS_GPU_RELATED=host: doc sets, counts and ranking on the host over a copy of the posting array
+					 * (nxs_related.h): the cross-check */
+	uint32_t	related_run;	/* NXS_GPU_RELATED_RUN (4096): postings of the flat array per workgroup of k_rt_scan; a multiple of
+					 * 64, 64 at least (one wavefront's worth) */
+	uint32_t	related_parts;	/* NXS_GPU_RELATED_PARTS (64): a plan's count row is cut into at most this many parts, one
+					 * workgroup each (k_rt_select) */
+	uint64_t	related_ws;	/* NXS_GPU_RELATED_WS (256 MiB): bytes of count rows per pass; the group is what fits (one plan
+					 * at least, 32 at most), a larger batch is cut into passes */
 };
 enum : uint32_t { COUNT_AUTO = 0, COUNT_TILE = 1, COUNT_REQ = 2, COUNT_SCAN = 3 };
 
@@ -420,6 +431,8 @@ struct nxsgpu_index {
 	struct ex_state_t *ex;
 	/* term vectors of docs (nxsgpu_doc_terms, nxs_gpu_docterms.hip): the same; nothing until the first call */
 	struct dv_state_t *dv;
+	/* related terms (nxsgpu_related, nxs_gpu_related.hip): the same; nothing until the first call */
+	struct rt_state_t *rt;
 };
 
 static inline uint32_t __device__ __host__
@@ -691,6 +704,9 @@ void	ex_free(nxsgpu_index_t *ix);		/* everything nxsgpu_explain has built (index
 
 /* ---- nxs_gpu_docterms.hip ---- */
 void	dv_free(nxsgpu_index_t *ix);		/* everything nxsgpu_doc_terms has built (index destroy) */
+
+/* ---- nxs_gpu_related.hip ---- */
+void	rt_free(nxsgpu_index_t *ix);		/* everything nxsgpu_related has built (index destroy) */
 
 /* ---- nxs_gpu_plan.hip ---- */
 void	delete_worklist(worklist_t *);

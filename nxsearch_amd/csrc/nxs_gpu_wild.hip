@@ -37,6 +37,7 @@
  * ranker (nxs_wild_rank) over a host copy of the BK image: the cross-check route.
  */
 #include "nxs_gpu_int.h"
+#include "nxs_gpu_dev.h"
 #include "nxs_wild.h"
 
 #define	WC_GROUP	256
@@ -66,30 +67,6 @@ wc_parts(uint32_t len, uint32_t cap)
 	const uint32_t tiles = (len + WC_GROUP - 1) / WC_GROUP;
 
 	return tiles < cap ? tiles : cap;
-}
-
-/* the group-wide minimum of `best` (s_w: one slot per wavefront; two barriers) */
-static __device__ __forceinline__ uint64_t
-wc_group_min(uint64_t best, uint64_t *s_w, unsigned tid)
-{
-	for (int o = 32; o; o >>= 1) {
-		const uint64_t c = (uint64_t)__shfl_xor((long long)best, o);
-		if (c < best) {
-			best = c;
-		}
-	}
-	if ((tid & 63) == 0) {
-		s_w[tid >> 6] = best;
-	}
-	__syncthreads();
-	best = s_w[0];
-	for (unsigned w = 1; w < WC_GROUP / WAVE; w++) {
-		if (s_w[w] < best) {
-			best = s_w[w];
-		}
-	}
-	__syncthreads();
-	return best;
 }
 
 __global__ void __launch_bounds__(WC_GROUP)
@@ -152,30 +129,7 @@ k_wc_match(const nxsgpu_bknode_t *__restrict__ bk, const uint8_t *__restrict__ b
 		}
 		__syncthreads();
 		if (s_flag[0] | s_flag[1] | s_flag[2] | s_flag[3]) {
-			/* round r delivers the r-th smallest key of the union: the smallest above round r - 1's (no
-			 * key is 0: term ids start at 1).  The kept keys sit in registers of threads 0 .. k - 1, so
-			 * s_top can be rewritten as the rounds go. */
-			const uint64_t kept = tid < k ? s_top[tid] : none;
-			uint64_t prev = 0;
-
-			for (uint32_t r = 0; r < k; r++) {
-				uint64_t best = none;
-
-				if (mine > prev) {
-					best = mine;
-				}
-				if (kept > prev && kept < best) {
-					best = kept;
-				}
-				best = wc_group_min(best, s_w, tid);
-				if (best == none) {
-					break;		/* (fewer than k so far: the slots from r on were ~0 already) */
-				}
-				if (tid == 0) {
-					s_top[r] = best;
-				}
-				prev = best;
-			}
+			group_topk_take<WC_GROUP>(mine, s_top, k, s_w, tid);
 		}
 		__syncthreads();
 	}
@@ -205,37 +159,13 @@ k_wc_merge(const uint64_t *__restrict__ partial, const uint2 *__restrict__ range
 	const uint2 rg = range[px];
 	const uint32_t n = wc_parts(rg.y - rg.x, cap) * k;
 	const uint64_t *list = partial + (size_t)px * cap * k;
-	const uint64_t none = ~0ull;
-	uint64_t mine = none, prev = 0;
-	uint32_t nout = 0;
+	const uint32_t nout = group_topk_merge<WC_GROUP>(list, n, k, s_w, tid, [&](uint32_t r, uint64_t best) {
+		const uint64_t at = (uint64_t)px * k + r;
 
-	if (tid < n) {
-		mine = list[tid];
-	}
-	for (uint32_t r = 0; r < k; r++) {
-		uint64_t best = none;
+		term_ids[at] = (uint32_t)best;
+		df[at] = ~(uint32_t)(best >> 32);
+	});
 
-		if (mine > prev) {
-			best = mine;
-		}
-		for (uint32_t i = tid + WC_GROUP; i < n; i += WC_GROUP) {
-			const uint64_t c = list[i];
-			if (c > prev && c < best) {
-				best = c;
-			}
-		}
-		best = wc_group_min(best, s_w, tid);
-		if (best == none) {
-			break;
-		}
-		if (tid == 0) {
-			const uint64_t at = (uint64_t)px * k + r;
-			term_ids[at] = (uint32_t)best;
-			df[at] = ~(uint32_t)(best >> 32);
-		}
-		prev = best;
-		nout++;
-	}
 	if (tid == 0) {
 		counts[px] = nout;
 	}

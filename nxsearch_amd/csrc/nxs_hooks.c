@@ -15,6 +15,7 @@
 #include "nxs_wild.h"
 #include "nxs_explain.h"
 #include "nxs_docterms.h"
+#include "nxs_related.h"
 
 char *
 nxs_test_query_repr(const char *query, char **errmsg)
@@ -268,6 +269,33 @@ uint64_t
 nxs_test_docterms_key(float w, uint32_t term)
 {
 	return nxs_dv_key(w, term);
+}
+
+/* nxs_related.h: the key of (c, df, term) under an order, the share, the predicate and the host ranker */
+uint64_t
+nxs_test_related_key(int order, uint32_t c, uint32_t df, uint32_t term)
+{
+	return nxs_rt_key(order, c, df, term);
+}
+
+float
+nxs_test_related_share(uint32_t c, uint32_t df)
+{
+	return nxs_rt_share(c, df);
+}
+
+bool
+nxs_test_related_eligible(uint32_t c, uint32_t df, uint32_t mincount, uint32_t mindf, uint32_t term, const uint32_t *excl,
+    uint32_t n_excl)
+{
+	return nxs_rt_eligible(c, df, mincount, mindf, term, excl, n_excl);
+}
+
+int
+nxs_test_related_rank(int order, const uint32_t *c, const uint32_t *df, uint32_t n_terms, uint32_t mincount,
+    uint32_t mindf, const uint32_t *excl, uint32_t n_excl, uint32_t k, uint32_t *out_ids, uint64_t *matches)
+{
+	return nxs_rt_rank(order, c, df, n_terms, mincount, mindf, excl, n_excl, k, out_ids, matches);
 }
 
 /* nxs_ex_ordinal for every q[i] over ids[0 .. n) (UINT64_MAX: not a live doc) */

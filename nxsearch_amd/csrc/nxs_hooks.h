@@ -147,5 +147,23 @@ int		nxs_test_docterms_lane(const uint64_t *dt, uint64_t n, bool bitmap, uint32_
 uint64_t	nxs_test_docterms_key(float w, uint32_t term);
 void		nxs_test_similar_drop(nxs_resp_t *, uint64_t doc, uint64_t limit);
 
+
+/* related terms: nxs_index_related's own parameters as it reads them (0, or -1 with the error declared), an
+ * nxs_sugg_t of the related kind built by hand (distance = c, the score is the share), and nxs_related.h: the key
+ * of (c, df, term) under order 0 ("count") / 1 ("share"), the share, the eligibility predicate and the host
+ * ranker over c[t], df[t], t = 1 .. n_terms (-> rows written, *matches exact; -1: out of memory) */
+int		nxs_test_related_params(nxs_t *, nxs_params_t *, unsigned *k, int *order, unsigned *mindf,
+		    unsigned *mincount, int *self);
+nxs_sugg_t *	nxs_test_related_build(const char *query, size_t query_len, uint64_t docs, uint64_t matches,
+		    unsigned count, const uint8_t *const *terms, const size_t *lens, const unsigned *cs,
+		    const uint64_t *dfs);
+uint64_t	nxs_test_related_key(int order, uint32_t c, uint32_t df, uint32_t term);
+float		nxs_test_related_share(uint32_t c, uint32_t df);
+bool		nxs_test_related_eligible(uint32_t c, uint32_t df, uint32_t mincount, uint32_t mindf, uint32_t term,
+		    const uint32_t *excl, uint32_t n_excl);
+int		nxs_test_related_rank(int order, const uint32_t *c, const uint32_t *df, uint32_t n_terms, uint32_t mincount,
+		    uint32_t mindf, const uint32_t *excl, uint32_t n_excl, uint32_t k, uint32_t *out_ids,
+		    uint64_t *matches);
+
 #endif /* NXS_TEST_HOOKS */
 #endif /* NXS_HOOKS_H */

@@ -2,7 +2,8 @@
  * nxs_lookup.c -- dictionary lookups by string: spelling suggestions
  * (nxs_index_suggest), prefix completions (nxs_index_complete) and wildcard
  * matches (nxs_index_wildcard); by doc: its term vector (nxs_index_doc_terms);
- * and the object all four return (nxs_sugg_t).
+ * by query: the terms of its matches (nxs_index_related); and the object all
+ * five return (nxs_sugg_t).
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -20,7 +21,7 @@ typedef struct {
 	size_t		len;
 	unsigned	dist;		/* (a term vector's: the doc's term count) */
 	uint64_t	df;
-	float		score;		/* a term vector's: rank(term, doc) */
+	float		score;		/* a term vector's: rank(term, doc); a related term's: its share c / df */
 } sugg_item_t;
 
 struct nxs_sugg {
@@ -28,14 +29,16 @@ struct nxs_sugg {
 	size_t		token_len;
 	bool		dropped;
 	int		kind;		/* SUGG_*: by nxs_index_complete / _wildcard `token` is the prefix / the pattern, the
-					 * JSON has its own shape; by nxs_index_doc_terms there is no string but doc_id */
+					 * JSON has its own shape; by nxs_index_doc_terms there is no string but doc_id; by
+					 * nxs_index_related `token` is the query as given, dist = c, docs = |M| */
 	uint64_t	doc_id;
+	uint64_t	docs;
 	uint64_t	matches;
 	unsigned	count;
 	sugg_item_t	items[];
 };
 
-enum { SUGG_SUGGEST = 0, SUGG_COMPLETE = 1, SUGG_WILD = 2, SUGG_DOC = 3 };
+enum { SUGG_SUGGEST = 0, SUGG_COMPLETE = 1, SUGG_WILD = 2, SUGG_DOC = 3, SUGG_RELATED = 4 };
 
 /* one block: the object, its items, the strings */
 static nxs_sugg_t *
@@ -61,6 +64,7 @@ sugg_build(const char *token, size_t token_len, bool dropped, uint64_t matches, 
 	sg->dropped = dropped;
 	sg->kind = SUGG_SUGGEST;
 	sg->doc_id = 0;
+	sg->docs = 0;
 	sg->matches = matches;
 	sg->count = count;
 	for (unsigned i = 0; i < count; i++) {
@@ -110,10 +114,20 @@ nxs_sugg_get(const nxs_sugg_t *sg, unsigned i, const char **term, size_t *len, u
 bool
 nxs_sugg_score(const nxs_sugg_t *sg, unsigned i, float *score)
 {
-	if (sg->kind != SUGG_DOC || i >= sg->count) {
+	if ((sg->kind != SUGG_DOC && sg->kind != SUGG_RELATED) || i >= sg->count) {
 		return false;
 	}
 	if (score) *score = sg->items[i].score;
+	return true;
+}
+
+bool
+nxs_sugg_docs(const nxs_sugg_t *sg, uint64_t *docs)
+{
+	if (sg->kind != SUGG_RELATED) {
+		return false;
+	}
+	if (docs) *docs = sg->docs;
 	return true;
 }
 
@@ -126,13 +140,14 @@ nxs_sugg_release(nxs_sugg_t *sg)
 /* {"token":"...","suggestions":[{"term":"...","distance":D,"df":N},...],"matches":M}; of a completion:
  * {"prefix":"...","completions":[{"term":"...","df":N},...],"matches":M}; of a wildcard match:
  * {"pattern":"...","terms":[{"term":"...","df":N},...],"matches":M}; of a term vector:
- * {"doc_id":N,"terms":[{"term":"...","tf":N,"df":N,"score":X},...],"matches":M} */
+ * {"doc_id":N,"terms":[{"term":"...","tf":N,"df":N,"score":X},...],"matches":M}; of related terms:
+ * {"query":"...","docs":N,"terms":[{"term":"...","count":N,"df":N,"score":X},...],"matches":M} */
 char *
 nxs_sugg_tojson(nxs_sugg_t *sg, size_t *len)
 {
-	static const char *const head[] = { "{\"token\":", "{\"prefix\":", "{\"pattern\":" };
-	static const char *const list[] = { ",\"suggestions\":[", ",\"completions\":[", ",\"terms\":[", ",\"terms\":[" };
-	size_t cap = 96 + 6 * sg->token_len, o = 0;
+	static const char *const head[] = { "{\"token\":", "{\"prefix\":", "{\"pattern\":", "", "{\"query\":" };
+	static const char *const list[] = { ",\"suggestions\":[", ",\"completions\":[", ",\"terms\":[", ",\"terms\":[", ",\"terms\":[" };
+	size_t cap = 128 + 6 * sg->token_len, o = 0;
 	char *s;
 
 	for (unsigned i = 0; i < sg->count; i++) {
@@ -146,14 +161,17 @@ nxs_sugg_tojson(nxs_sugg_t *sg, size_t *len)
 	} else {
 		o += (size_t)sprintf(s + o, "%s", head[sg->kind]);
 		o += json_str(s + o, sg->token, sg->token_len);
+		if (sg->kind == SUGG_RELATED) {
+			o += (size_t)sprintf(s + o, ",\"docs\":%llu", (unsigned long long)sg->docs);
+		}
 	}
 	o += (size_t)sprintf(s + o, "%s", list[sg->kind]);
 	for (unsigned i = 0; i < sg->count; i++) {
 		o += (size_t)sprintf(s + o, "%s{\"term\":", i ? "," : "");
 		o += json_str(s + o, sg->items[i].term, sg->items[i].len);
-		if (sg->kind == SUGG_DOC) {
-			o += (size_t)sprintf(s + o, ",\"tf\":%u,\"df\":%llu,\"score\":", sg->items[i].dist,
-			    (unsigned long long)sg->items[i].df);
+		if (sg->kind == SUGG_DOC || sg->kind == SUGG_RELATED) {
+			o += (size_t)sprintf(s + o, ",\"%s\":%u,\"df\":%llu,\"score\":", sg->kind == SUGG_DOC ? "tf" : "count",
+			    sg->items[i].dist, (unsigned long long)sg->items[i].df);
 			o += fmt_real(s + o, (double)sg->items[i].score);
 			s[o++] = '}';
 		} else if (sg->kind != SUGG_SUGGEST) {
@@ -758,6 +776,182 @@ nxs_index_doc_terms(nxs_index_t *idx, nxs_params_t *params, nxs_doc_id_t doc)
 	(void)nxs_index_doc_terms_batch(idx, params, &doc, 1, &sg, NULL);	/* (as nxs_index_suggest) */
 	return sg;
 }
+
+/* ---- related terms (nxs_index_related) ---------------------------------------------------- */
+
+/* related terms as the device reports them into an object; NULL: out of memory / an unknown term (declared) */
+static nxs_sugg_t *
+related_build(nxs_index_t *idx, const char *query, uint64_t docs, uint64_t matches, unsigned count, const uint32_t *ids,
+    const uint32_t *c, const uint32_t *df, nxs_err_t *code)
+{
+	const uint8_t *terms[NXS_SUGGEST_MAX] = { NULL };
+	size_t tlens[NXS_SUGGEST_MAX] = { 0 };
+	unsigned dists[NXS_SUGGEST_MAX] = { 0 };
+	uint64_t dfs[NXS_SUGGEST_MAX] = { 0 };
+	nxs_sugg_t *sg;
+
+	for (unsigned j = 0; j < count; j++) {
+		if (ids[j] < 1 || ids[j] > idx->last_id || df[j] == 0) {
+			*code = NXS_ERR_FATAL;
+			nxs_decl_err(idx->nxs, *code, "the device named an unknown term for a related query");
+			return NULL;
+		}
+		terms[j] = idx->terms[ids[j]].val;
+		tlens[j] = idx->terms[ids[j]].len;
+		dists[j] = c[j];
+		dfs[j] = df[j];
+	}
+	if ((sg = sugg_build(query, strlen(query), false, matches, count, terms, tlens, dists, dfs)) == NULL) {
+		*code = NXS_ERR_SYSTEM;
+		nxs_decl_err(idx->nxs, *code, "out of memory");
+		return NULL;
+	}
+	sg->kind = SUGG_RELATED;
+	sg->docs = docs;
+	for (unsigned j = 0; j < count; j++) {
+		sg->items[j].score = nxs_rt_share(c[j], df[j]);
+	}
+	return sg;
+}
+
+/*
+ * The front half is a search's (plan_batch: parse, filters, blocking fuzzy / prefix / wildcard resolution, truth
+ * table or postfix program); the plan's resolved term ids are the exclusion list.  The fixed-size plans go to
+ * nxsgpu_related in one call.
+ */
+int
+nxs_index_related_batch(nxs_index_t *idx, nxs_params_t *params, const char *const *queries, size_t n,
+    nxs_sugg_t **out, nxs_err_t *errs)
+{
+	nxs_t *nxs = idx->nxs;
+	search_params_t sp;
+	related_params_t rp;
+	qprep_t *prep = NULL;
+	nxsgpu_query_t *plans = NULL;
+	uint32_t *rows = NULL, *slot = NULL;
+	size_t np = 0;
+	int ret = -1, failed = 0;
+
+	nxs_clear_error(nxs);
+	outs_clear(out, errs, n);
+	if (get_related_params(nxs, params, &rp) == -1 || get_search_params(idx, params, &sp) == -1 ||
+	    lookup_enter(idx, "related", n, false) == -1) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	prep = calloc(n, sizeof(*prep));
+	plans = malloc(n * sizeof(*plans));
+	slot = malloc(n * sizeof(*slot));
+	rows = malloc(n * (3 * (size_t)rp.k + 3) * sizeof(*rows));
+	if (!prep || !plans || !slot || !rows) {
+		nxs_decl_err(nxs, NXS_ERR_SYSTEM, "out of memory");
+		goto out;
+	}
+	if (plan_batch(idx, &sp, queries, NULL, n, prep) == -1) {
+		goto out;
+	}
+	for (size_t i = 0; i < n; i++) {
+		slot[i] = UINT32_MAX;
+		if (!prep[i].errcode && !prep[i].wide && !prep[i].empty) {
+			slot[i] = (uint32_t)np;
+			plans[np++] = prep[i].plan;
+		}
+	}
+	{
+		uint32_t *ids = rows, *c = ids + np * rp.k, *df = c + np * rp.k, *counts = df + np * rp.k;
+		uint32_t *matches = counts + np, *docs = matches + np;
+
+		if (np && nxsgpu_related(idx->dev, sp.algo, plans, (uint32_t)np, rp.order, rp.mindf, rp.mincount, rp.self, rp.k,
+		    ids, c, df, counts, matches, docs) != 0) {
+			nxs_decl_err(nxs, NXS_ERR_FATAL, "device related pass failed: %s", nxsgpu_last_error());
+			goto out;
+		}
+		for (size_t i = 0; i < n; i++) {
+			nxs_err_t code = prep[i].errcode;
+			const size_t s = slot[i];
+
+			if (code) {
+				/* what a search reports for the string */
+				nxs_decl_err(nxs, code, "%s", prep[i].errmsg ? prep[i].errmsg : "");
+			} else if (prep[i].wide) {
+				code = NXS_ERR_LIMIT;
+				nxs_decl_err(nxs, code, "related is not available for a query of more than %u terms", NXSGPU_MAX_TOKENS);
+			} else if (s == UINT32_MAX) {
+				/* resolves to nothing: an empty list */
+				out[i] = related_build(idx, queries[i], 0, 0, 0, NULL, NULL, NULL, &code);
+			} else {
+				out[i] = related_build(idx, queries[i], docs[s], matches[s], counts[s] <= rp.k ? counts[s] : rp.k,
+				    ids + s * rp.k, c + s * rp.k, df + s * rp.k, &code);
+			}
+			if (!out[i]) {
+				if (errs) {
+					errs[i] = code;
+				}
+				failed++;
+			}
+		}
+	}
+	ret = failed;
+out:
+	for (size_t i = 0; prep && i < n; i++) {
+		nxs_query_release(&prep[i]);
+	}
+	free(prep);
+	free(plans);
+	free(slot);
+	free(rows);
+	return ret;
+}
+
+nxs_sugg_t *
+nxs_index_related(nxs_index_t *idx, nxs_params_t *params, const char *query, size_t len)
+{
+	nxs_sugg_t *sg = NULL;
+
+	(void)len;	/* (as nxs_index_search: the lexer stops at the NUL byte) */
+	(void)nxs_index_related_batch(idx, params, &query, 1, &sg, NULL);	/* (as nxs_index_suggest) */
+	return sg;
+}
+
+#ifdef NXS_TEST_HOOKS
+/* the parameters as nxs_index_related reads its own keys: 0, or -1 with the error declared */
+int
+nxs_test_related_params(nxs_t *nxs, nxs_params_t *params, unsigned *k, int *order, unsigned *mindf, unsigned *mincount,
+    int *self)
+{
+	related_params_t rp;
+
+	nxs_clear_error(nxs);
+	if (get_related_params(nxs, params, &rp) == -1) {
+		return -1;
+	}
+	*k = rp.k;
+	*order = rp.order;
+	*mindf = rp.mindf;
+	*mincount = rp.mincount;
+	*self = rp.self;
+	return 0;
+}
+
+/* an nxs_sugg_t of the related kind built by hand (the scores are the shares c / df) */
+nxs_sugg_t *
+nxs_test_related_build(const char *query, size_t query_len, uint64_t docs, uint64_t matches, unsigned count,
+    const uint8_t *const *terms, const size_t *lens, const unsigned *cs, const uint64_t *dfs)
+{
+	nxs_sugg_t *sg = sugg_build(query, query_len, false, matches, count, terms, lens, cs, dfs);
+
+	if (sg) {
+		sg->kind = SUGG_RELATED;
+		sg->docs = docs;
+		for (unsigned i = 0; i < count; i++) {
+			sg->items[i].score = nxs_rt_share(cs[i], (uint32_t)dfs[i]);
+		}
+	}
+	return sg;
+}
+#endif /* NXS_TEST_HOOKS */
 
 #ifdef NXS_TEST_HOOKS
 /* the parameters as nxs_index_doc_terms / nxs_index_similar read them: 0, or -1 with the error declared */

@@ -632,3 +632,58 @@ nxs_test_explain_params(nxs_t *nxs, nxs_params_t *params, int *explain)
 	return 0;
 }
 #endif /* NXS_TEST_HOOKS */
+
+/*
+ * The parameters of nxs_index_related, validated as the docterms_* keys are: "related_limit" (uint,
+ * 1..NXS_SUGGEST_MAX, default 5), "related_order" ("count", the default, or "share"), "related_mindf" and
+ * "related_mincount" (uint >= 1, default 1), "related_self" (bool, default false).  0, or -1 with
+ * NXS_ERR_INVALID and a message that names the key.
+ */
+int
+get_related_params(nxs_t *nxs, const nxs_params_t *params, related_params_t *rp)
+{
+	static const char *const floors[] = { "related_mindf", "related_mincount" };
+	unsigned *const floor_of[] = { &rp->mindf, &rp->mincount };
+	const char *s;
+	uint64_t v;
+	bool fl;
+
+	rp->k = 5;
+	rp->order = NXS_RT_COUNT;
+	rp->mindf = 1;
+	rp->mincount = 1;
+	rp->self = false;
+	if (!params) {
+		return 0;
+	}
+	if (nxs_params_get_uint(params, "related_limit", &v) == 0) {
+		if (v < 1 || v > NXS_SUGGEST_MAX) {
+			nxs_decl_err(nxs, NXS_ERR_INVALID, "invalid related_limit (1..%d)", NXS_SUGGEST_MAX);
+			return -1;
+		}
+		rp->k = (unsigned)v;
+	}
+	for (int i = 0; i < 2; i++) {
+		if (nxs_params_get_uint(params, floors[i], &v) == 0) {
+			if (v < 1 || v > UINT32_MAX) {
+				nxs_decl_err(nxs, NXS_ERR_INVALID, "invalid %s (>= 1)", floors[i]);
+				return -1;
+			}
+			*floor_of[i] = (unsigned)v;
+		}
+	}
+	if ((s = nxs_params_get_str(params, "related_order")) != NULL) {
+		if (strcmp(s, "count") == 0) {
+			rp->order = NXS_RT_COUNT;
+		} else if (strcmp(s, "share") == 0) {
+			rp->order = NXS_RT_SHARE;
+		} else {
+			nxs_decl_err(nxs, NXS_ERR_INVALID, "invalid related_order (\"count\" or \"share\")");
+			return -1;
+		}
+	}
+	if (nxs_params_get_bool(params, "related_self", &fl) == 0 && fl) {
+		rp->self = true;
+	}
+	return 0;
+}
