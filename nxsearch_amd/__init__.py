@@ -100,6 +100,7 @@ NXS_H_SYMBOLS = [
 ]
 # csrc/nxs_hooks.h: test hooks + bench accessors, only in builds with -DNXS_TEST_HOOKS (the default)
 NXS_HOOK_SYMBOLS = ["nxs_index_device", "nxs_index_host_profile", "nxs_index_shard_info", "nxs_test_pool", "nxs_test_assemble",
+                    "nxs_test_index_image", "nxsgpu_test_index_image",
                     "nxs_test_fixup_scan", "nxs_test_inject_failure", "nxs_test_count_tile_widths",
                     "nxs_test_suggest_host", "nxs_test_suggest_params", "nxs_test_sugg_build",
                     "nxs_test_complete_host", "nxs_test_complete_params", "nxs_test_compl_build",
@@ -136,6 +137,17 @@ NXS_GPU_H_SYMBOLS = [
     "nxsgpu_doc_terms", "nxsgpu_doc_terms_profile",
     "nxsgpu_related", "nxsgpu_related_profile",
 ]
+
+# nxs_test_index_image (csrc/nxs_hooks.h): part numbers and the order of the scalars, as nxsgpu_test_index_image
+# (csrc/nxs_gpu_index.hip) has them
+IMG_SCALARS = 0
+IMG_SCALAR_NAMES = ["n_docs", "n_post", "n_terms", "hdr_doc_count", "hdr_token_count", "max_tf", "bm_words",
+                    "dense_q8_stride", "cap_post", "scanm_dens", "outl_share", "bm_share", "algo_on", "switches"]
+IMG_PARTS = {"doc_ids": (1, "<u8"), "doc_len": (2, "<u4"), "post_off": (3, "<u8"), "post_dt": (4, "<u8"),
+             "post": (5, "post"), "outl_post": (6, "post"), "maximp": (7, "<u4"), "dense_terms": (8, "<u4"),
+             "dense_col": (9, "<u4"), "dense_q8": (10, "u1"), "outl_off": (11, "<u8"), "outl_cap": (12, "<u4"),
+             "outl_max": (13, "<u4"), "bm_terms": (14, "<u4"), "blkmap": (15, "<u8"), "bmrank": (16, "<u4")}
+IMG_PER_ALGO = (5, 7, 9)
 
 _lib = None
 
@@ -948,6 +960,44 @@ class Index:
                 "fuzzy_wait_ms": round(1e3 * out[8] / n, 4), "front_ms": round(1e3 * out[9] / n, 4),
                 "fuzzy_launch_ms": round(1e3 * out[10] / n, 4), "back_ms": round(1e3 * out[11] / n, 4),
                 "batches": int(out[4]), "exact_requeries": int(out[5])}
+
+    def device_image(self, algos=(0, 1)):
+        """nxs_test_index_image(): the device index read back as numpy arrays, for the tests that compare it
+        with a host model.  -> {"scalars": {...}, name: array, ...}; the parts of a ranking function are keyed
+        (name, algo) with algo 0 = TF-IDF, 1 = BM25.  A part that is not materialised is an empty array.
+        Postings are structured arrays (doc u32, imp u32 = the f32's bits).  Not while batches are in flight."""
+        import numpy as np
+        L = lib()
+        L.nxs_test_index_image.restype = C.c_int
+        L.nxs_test_index_image.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+
+        def part(no, dtype, algo=0):
+            need = C.c_size_t()
+            if L.nxs_test_index_image(self._h, no, algo, None, 0, C.byref(need)) != 0:
+                self.nxs._raise()
+            buf = np.empty(need.value, dtype=np.uint8)
+            if need.value:
+                got = C.c_size_t()
+                if L.nxs_test_index_image(self._h, no, algo, buf.ctypes.data, buf.nbytes, C.byref(got)) != 0:
+                    self.nxs._raise()
+                assert got.value == need.value, (no, algo, got.value, need.value)
+            return buf.view(dtype)
+
+        raw = part(IMG_SCALARS, np.uint64)
+        sc = {name: int(raw[i]) for i, name in enumerate(IMG_SCALAR_NAMES)}
+        sc["scanm_dens"] = float(raw[9:10].view(np.float64)[0])
+        out = {"scalars": sc}
+        post_t = np.dtype([("doc", "<u4"), ("imp", "<u4")])
+        for name, (no, dtype) in IMG_PARTS.items():
+            dtype = post_t if dtype == "post" else np.dtype(dtype)
+            if no in IMG_PER_ALGO:
+                for a in algos:
+                    out[(name, a)] = part(no, dtype, a)
+            else:
+                out[name] = part(no, dtype)
+        if sc["dense_q8_stride"] and len(out["dense_q8"]):
+            out["dense_q8"] = out["dense_q8"].reshape(-1, sc["dense_q8_stride"])
+        return out
 
     def reconfigure(self):
         """Re-read the NXS_GPU_* switches (parsed once at open); tests/tools."""

@@ -1919,6 +1919,180 @@ nxsgpu_index_set_global_df(nxsgpu_index_t *ix, const uint32_t *df, uint32_t n_te
 
 extern "C" uint64_t nxsgpu_index_impact_passes(const nxsgpu_index_t *ix) { return ix->n_impact_passes; }
 
+#ifdef NXS_TEST_HOOKS
+/*
+ * The device half of nxs_test_index_image (nxs_hooks.h): one part of the index image, read back for
+ * the tests that compare it with a host model (tests/test_index_image.py).  *need = the part's bytes
+ * (0: the part is not materialised); they are copied to `out` if cap holds them.  Nothing on the
+ * device changes: the index's streams are waited for, the device arrays come back by plain hipMemcpy.
+ * The part numbers and the order of the scalars are restated in nxsearch_amd/__init__.py (IMG_*).
+ */
+extern "C" int
+nxsgpu_test_index_image(nxsgpu_index_t *ix, int part, int algo, void *out, size_t cap, size_t *need)
+{
+	enum { P_SCALARS, P_DOC_IDS, P_DOC_LEN, P_POST_OFF, P_POST_DT, P_POST, P_OUTL_POST, P_MAXIMP, P_DENSE_TERMS,
+	    P_DENSE_COL, P_DENSE_Q8, P_OUTL_OFF, P_OUTL_CAP, P_OUTL_MAX, P_BM_TERMS, P_BLKMAP, P_BMRANK, P_COUNT };
+	const bool per_algo = part == P_POST || part == P_MAXIMP || part == P_DENSE_COL;
+	const size_t nc = ix->dense_terms.size(), rows = ix->bm_terms.size();
+	const bool tfidf = ix->algo_on[NXSGPU_TF_IDF];
+	/* the outlier tables describe d_post[TF_IDF]; a failed pass leaves offsets without caps */
+	const bool outl = tfidf && ix->outl_off.size() == nc + 1 && ix->outl_cap.size() == nc && ix->outl_max.size() == nc;
+	const void *src = NULL;		/* host memory, or (dev) device memory */
+	bool dev = false;
+	size_t len = 0;
+	uint64_t sc[16] = { 0 };
+
+	*need = 0;
+	if (part < 0 || part >= P_COUNT || (per_algo && algo != NXSGPU_BM25 && algo != NXSGPU_TF_IDF)) {
+		set_error("nxsgpu_test_index_image: no part %d of ranking function %d", part, algo);
+		return -1;
+	}
+	if (nxsgpu_batches_in_flight(ix)) {
+		set_error("nxsgpu_test_index_image: batches are in flight");
+		return -1;
+	}
+	if (hipSetDevice(ix->device) != hipSuccess) {
+		set_error("hipSetDevice failed");
+		return -1;
+	}
+	{
+		const hipStream_t sts[] = { ix->stream, ix->stream2, ix->stream3, ix->stream_up, ix->stream_down, ix->stream_fz,
+		    ix->stream_rp[1], ix->xstream[0], ix->xstream[1], ix->xstream[2], ix->stream_cnt };
+		for (hipStream_t st : sts) {
+			if (st && hipStreamSynchronize(st) != hipSuccess) {
+				set_error("nxsgpu_test_index_image: hipStreamSynchronize failed");
+				return -1;
+			}
+		}
+	}
+	switch (part) {
+	case P_SCALARS:
+		sc[0] = ix->n_docs;
+		sc[1] = ix->n_post;
+		sc[2] = ix->n_terms;
+		sc[3] = ix->hdr_doc_count;
+		sc[4] = ix->hdr_token_count;
+		sc[5] = ix->max_tf;
+		sc[6] = ix->bm_words;
+		sc[7] = ix->dense_q8_stride;
+		sc[8] = ix->cap_post;
+		memcpy(&sc[9], &ix->cfg.scanm_dens, 8);
+		sc[10] = ix->cfg.outl_share;
+		sc[11] = ix->cfg.bm_share;
+		sc[12] = (ix->algo_on[0] ? 1u : 0u) | (ix->algo_on[1] ? 2u : 0u);
+		sc[13] = (ix->cfg.use_blkmap ? 1u : 0u) | (ix->cfg.tfidf_drop ? 2u : 0u) | (ix->cfg.use_scans_drop ? 4u : 0u);
+		src = sc;
+		len = sizeof(sc);
+		break;
+	case P_DOC_IDS:
+		src = ix->d_doc_ids;
+		len = ix->n_docs * 8;
+		dev = true;
+		break;
+	case P_DOC_LEN:
+		src = ix->d_doc_len;
+		len = ix->n_docs * 4;
+		dev = true;
+		break;
+	case P_POST_OFF:
+		src = ix->d_post_off;
+		len = ((size_t)ix->n_terms + 2) * 8;
+		dev = true;
+		break;
+	case P_POST_DT:
+		src = ix->d_post_dt;
+		len = ix->n_post * 8;
+		dev = true;
+		break;
+	case P_POST:
+		if (ix->algo_on[algo]) {
+			src = ix->d_post[algo];
+			len = ix->n_post * sizeof(posting_t);
+			dev = true;
+		}
+		break;
+	case P_OUTL_POST:
+		if (outl && ix->outl_off[nc] <= post_elems(ix, NXSGPU_TF_IDF)) {
+			src = ix->d_post[NXSGPU_TF_IDF] + ix->outl_off[0];
+			len = (ix->outl_off[nc] - ix->outl_off[0]) * sizeof(posting_t);
+			dev = true;
+		}
+		break;
+	case P_MAXIMP:
+		if (ix->algo_on[algo]) {
+			src = ix->h_maximp[algo].data();
+			len = ix->h_maximp[algo].size() * 4;
+		}
+		break;
+	case P_DENSE_TERMS:
+		src = ix->dense_terms.data();
+		len = nc * 4;
+		break;
+	case P_DENSE_COL:
+		if (ix->algo_on[algo] && ix->d_dense_col[algo] && nc * ix->n_docs <= ix->dense_cap[algo]) {
+			src = ix->d_dense_col[algo];
+			len = nc * ix->n_docs * 4;
+			dev = true;
+		}
+		break;
+	case P_DENSE_Q8:
+		if (ix->cfg.use_scans_drop && ix->algo_on[NXSGPU_BM25] && ix->d_dense_q8 && nc * ix->dense_q8_stride <= ix->dense_q8_cap) {
+			src = ix->d_dense_q8;
+			len = nc * ix->dense_q8_stride;
+			dev = true;
+		}
+		break;
+	case P_OUTL_OFF:
+		if (outl) {
+			src = ix->outl_off.data();
+			len = (nc + 1) * 8;
+		}
+		break;
+	case P_OUTL_CAP:
+		if (outl) {
+			src = ix->outl_cap.data();
+			len = nc * 4;
+		}
+		break;
+	case P_OUTL_MAX:
+		if (outl) {
+			src = ix->outl_max.data();
+			len = nc * 4;
+		}
+		break;
+	case P_BM_TERMS:
+		src = ix->bm_terms.data();
+		len = rows * 4;
+		break;
+	case P_BLKMAP:
+		if (rows && ix->d_blkmap && rows * (ix->bm_words + 1) <= ix->bm_cap) {
+			src = ix->d_blkmap;
+			len = rows * ix->bm_words * 8;
+			dev = true;
+		}
+		break;
+	case P_BMRANK:
+		if (rows && ix->d_bmrank && rows * (ix->bm_words + 1) <= ix->bm_cap) {
+			src = ix->d_bmrank;
+			len = rows * (ix->bm_words + 1) * 4;
+			dev = true;
+		}
+		break;
+	}
+	*need = len;
+	if (!len || !out || cap < len) {
+		return 0;
+	}
+	if (!dev) {
+		memcpy(out, src, len);
+	} else if (hipMemcpy(out, src, len, hipMemcpyDeviceToHost) != hipSuccess) {
+		set_error("nxsgpu_test_index_image: hipMemcpy of part %d failed", part);
+		return -1;
+	}
+	return 0;
+}
+#endif /* NXS_TEST_HOOKS */
+
 extern "C" void
 nxsgpu_results_free(nxsgpu_results_t *res)
 {

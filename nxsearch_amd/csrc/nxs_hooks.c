@@ -298,6 +298,27 @@ nxs_test_related_rank(int order, const uint32_t *c, const uint32_t *df, uint32_t
 	return nxs_rt_rank(order, c, df, n_terms, mincount, mindf, excl, n_excl, k, out_ids, matches);
 }
 
+/*
+ * One part of the device index image (nxs_hooks.h): the host half only finds the device index and carries the
+ * error over; the part is read where its arrays live (nxs_gpu_index.hip).  0, or -1 with the error declared.
+ */
+int
+nxs_test_index_image(nxs_index_t *idx, int part, int algo, void *out, size_t cap, size_t *need)
+{
+	struct nxsgpu_index *dev = nxs_index_device(idx);
+
+	*need = 0;
+	if (!dev) {
+		nxs_decl_err(idx->nxs, NXS_ERR_INVALID, "the index has no device image");
+		return -1;
+	}
+	if (nxsgpu_test_index_image(dev, part, algo, out, cap, need) != 0) {
+		nxs_decl_err(idx->nxs, NXS_ERR_SYSTEM, "%s", nxsgpu_last_error());
+		return -1;
+	}
+	return 0;
+}
+
 /* nxs_ex_ordinal for every q[i] over ids[0 .. n) (UINT64_MAX: not a live doc) */
 void
 nxs_test_explain_ordinal(const uint64_t *ids, uint64_t n, const uint64_t *q, size_t nq, uint64_t *out)

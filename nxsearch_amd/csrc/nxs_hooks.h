@@ -26,6 +26,17 @@ void		nxs_index_shard_info(nxs_index_t *, uint64_t out[4]);
 /* the device-side handle behind an index (nxs_gpu.h): pre-resolved plans, results left in HBM */
 struct nxsgpu_index;
 struct nxsgpu_index *nxs_index_device(nxs_index_t *);
+/*
+ * One part of the device index image, read back: scalars, doc tables and CSR, the impacts and per-term maxima of
+ * a ranking function, the dense terms' columns (f32 and byte form) with the TF-IDF caps and outlier lists, the
+ * block-presence bitmaps and rank directories (the parts and the scalars' order: nxsgpu_test_index_image in
+ * nxs_gpu_index.hip, IMG_* in nxsearch_amd/__init__.py).  *need = the part's bytes, copied to `out` if cap
+ * holds them; a part that is not materialised has 0 bytes.  Refused while batches are in flight; waits for the
+ * index's streams, copies with hipMemcpy and changes nothing on the device.  0, or -1 with the error declared.
+ */
+int		nxs_test_index_image(nxs_index_t *, int part, int algo, void *out, size_t cap, size_t *need);
+/* ... its device half (nxs_gpu_index.hip); the error is nxsgpu_last_error() */
+int		nxsgpu_test_index_image(struct nxsgpu_index *, int part, int algo, void *out, size_t cap, size_t *need);
 /* the plan cache (query string -> compiled plan) on / off at run time */
 void		nxs_index_set_plan_cache(nxs_index_t *, int on);
 

@@ -19,12 +19,13 @@ def _pad32k(b: bytes) -> bytes:
 
 def terms_image(terms, totals, pad=True) -> bytes:
     """terms: list[bytes] in term-id order; totals: list[int]."""
-    body = b""
+    parts = []          # (joined once: appending to a bytes object copies it every time)
     for t, tot in zip(terms, totals):
         blk = struct.pack(">H", len(t)) + t + b"\0"
         blk += b"\0" * (-len(blk) % 8)
         blk += struct.pack(">Q", tot)
-        body += blk
+        parts.append(blk)
+    body = b"".join(parts)
     hdr = b"NXS_T" + bytes([1, 0, 0]) + struct.pack(">II", len(body), 0)
     img = hdr + body
     return _pad32k(img) if pad else img
@@ -33,11 +34,12 @@ def terms_image(terms, totals, pad=True) -> bytes:
 def dtmap_image(blocks, token_count, doc_count, pad=True) -> bytes:
     """blocks: list of (doc_id, doc_len, [(term_id, count), ...]);
     a tombstone is (doc_id, 0, [])."""
-    body = b""
+    parts = []
     for doc_id, doc_len, pairs in blocks:
-        body += struct.pack(">QII", doc_id, doc_len, len(pairs))
-        for tid, cnt in pairs:
-            body += struct.pack(">II", tid, cnt)
+        parts.append(struct.pack(">QII", doc_id, doc_len, len(pairs)))
+        if pairs:
+            parts.append(struct.pack(">%dI" % (2 * len(pairs)), *[x for p in pairs for x in p]))
+    body = b"".join(parts)
     hdr = (b"NXS_D" + bytes([1, 0, 0]) +
            struct.pack(">QQII", len(body), token_count, doc_count, 0))
     img = hdr + body
