@@ -147,6 +147,7 @@ IMG_PARTS = {"doc_ids": (1, "<u8"), "doc_len": (2, "<u4"), "post_off": (3, "<u8"
              "post": (5, "post"), "outl_post": (6, "post"), "maximp": (7, "<u4"), "dense_terms": (8, "<u4"),
              "dense_col": (9, "<u4"), "dense_q8": (10, "u1"), "outl_off": (11, "<u8"), "outl_cap": (12, "<u4"),
              "outl_max": (13, "<u4"), "bm_terms": (14, "<u4"), "blkmap": (15, "<u8"), "bmrank": (16, "<u4")}
+IMG_DF_GLOBAL = 17      # u32[T + 2], a doc shard's collection-wide df (N4); no bytes on a whole index
 IMG_PER_ALGO = (5, 7, 9)
 
 _lib = None
@@ -964,7 +965,8 @@ class Index:
     def device_image(self, algos=(0, 1)):
         """nxs_test_index_image(): the device index read back as numpy arrays, for the tests that compare it
         with a host model.  -> {"scalars": {...}, name: array, ...}; the parts of a ranking function are keyed
-        (name, algo) with algo 0 = TF-IDF, 1 = BM25.  A part that is not materialised is an empty array.
+        (name, algo) with algo 0 = TF-IDF, 1 = BM25.  A part that is not materialised is an empty array;
+        "df_global" (a doc shard's collection-wide df) is None on an index that is not a shard.
         Postings are structured arrays (doc u32, imp u32 = the f32's bits).  Not while batches are in flight."""
         import numpy as np
         L = lib()
@@ -997,6 +999,8 @@ class Index:
                 out[name] = part(no, dtype)
         if sc["dense_q8_stride"] and len(out["dense_q8"]):
             out["dense_q8"] = out["dense_q8"].reshape(-1, sc["dense_q8_stride"])
+        dfg = part(IMG_DF_GLOBAL, np.dtype("<u4"))
+        out["df_global"] = dfg if dfg.size else None
         return out
 
     def reconfigure(self):

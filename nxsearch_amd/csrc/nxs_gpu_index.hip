@@ -1922,7 +1922,7 @@ extern "C" uint64_t nxsgpu_index_impact_passes(const nxsgpu_index_t *ix) { retur
 #ifdef NXS_TEST_HOOKS
 /*
  * The device half of nxs_test_index_image (nxs_hooks.h): one part of the index image, read back for
- * the tests that compare it with a host model (tests/test_index_image.py).  *need = the part's bytes
+ * the tests that compare it with a host model (tests/test_index_image.py, tests/test_docshard_image.py).  *need = the part's bytes
  * (0: the part is not materialised); they are copied to `out` if cap holds them.  Nothing on the
  * device changes: the index's streams are waited for, the device arrays come back by plain hipMemcpy.
  * The part numbers and the order of the scalars are restated in nxsearch_amd/__init__.py (IMG_*).
@@ -1931,7 +1931,7 @@ extern "C" int
 nxsgpu_test_index_image(nxsgpu_index_t *ix, int part, int algo, void *out, size_t cap, size_t *need)
 {
 	enum { P_SCALARS, P_DOC_IDS, P_DOC_LEN, P_POST_OFF, P_POST_DT, P_POST, P_OUTL_POST, P_MAXIMP, P_DENSE_TERMS,
-	    P_DENSE_COL, P_DENSE_Q8, P_OUTL_OFF, P_OUTL_CAP, P_OUTL_MAX, P_BM_TERMS, P_BLKMAP, P_BMRANK, P_COUNT };
+	    P_DENSE_COL, P_DENSE_Q8, P_OUTL_OFF, P_OUTL_CAP, P_OUTL_MAX, P_BM_TERMS, P_BLKMAP, P_BMRANK, P_DF_GLOBAL, P_COUNT };
 	const bool per_algo = part == P_POST || part == P_MAXIMP || part == P_DENSE_COL;
 	const size_t nc = ix->dense_terms.size(), rows = ix->bm_terms.size();
 	const bool tfidf = ix->algo_on[NXSGPU_TF_IDF];
@@ -2077,6 +2077,11 @@ nxsgpu_test_index_image(nxsgpu_index_t *ix, int part, int algo, void *out, size_
 			len = rows * (ix->bm_words + 1) * 4;
 			dev = true;
 		}
+		break;
+	case P_DF_GLOBAL:
+		/* doc-sharded mode (N4): the collection-wide df the idf tables come from; empty on a whole index */
+		src = ix->df_global.data();
+		len = ix->df_global.size() * 4;
 		break;
 	}
 	*need = len;

@@ -29,8 +29,8 @@ struct nxsgpu_index *nxs_index_device(nxs_index_t *);
 /*
  * One part of the device index image, read back: scalars, doc tables and CSR, the impacts and per-term maxima of
  * a ranking function, the dense terms' columns (f32 and byte form) with the TF-IDF caps and outlier lists, the
- * block-presence bitmaps and rank directories (the parts and the scalars' order: nxsgpu_test_index_image in
- * nxs_gpu_index.hip, IMG_* in nxsearch_amd/__init__.py).  *need = the part's bytes, copied to `out` if cap
+ * block-presence bitmaps and rank directories, a doc shard's collection-wide df (the parts and the scalars' order:
+ * nxsgpu_test_index_image in nxs_gpu_index.hip, IMG_* in nxsearch_amd/__init__.py).  *need = the part's bytes, copied to `out` if cap
  * holds them; a part that is not materialised has 0 bytes.  Refused while batches are in flight; waits for the
  * index's streams, copies with hipMemcpy and changes nothing on the device.  0, or -1 with the error declared.
  */

@@ -22,111 +22,12 @@ import oracle_lib as O
 pytestmark = pytest.mark.gpu
 
 ENV = {"NXS_GPU_SCANM_DENS": "0.05", "NXS_GPU_SCANS_DROP": "1", "NXS_GPU_BM_SHARE": str(1 << 30)}
-ALGO_NAME = {T.TF_IDF: "TF-IDF", T.BM25: "BM25"}
+ALGO_NAME = T.ALGO_NAME
 
 
-def flat_rows(img):
-    """-> (row of every posting, its ordinal, its tf)"""
-    off = img["post_off"].astype(np.int64)
-    dt = img["post_dt"]
-    row = np.repeat(np.arange(len(off) - 1), np.diff(off))
-    return off, row, (dt >> np.uint64(32)).astype(np.int64), (dt & np.uint64(0xffffffff)).astype(np.int64)
-
-
-def check_image(img, m, max_tf, ctx):
-    """Every array of one image against the model m (whose ordinal table is this index's)."""
-    sc = img["scalars"]
-    n_docs, T_ = len(m.ord_ids), m.n_terms
-    P = sum(m.df.values())
-    # ---- scalars
-    assert sc["n_docs"] == n_docs and sc["n_terms"] == T_ and sc["n_post"] == P, (ctx, sc)
-    assert sc["hdr_doc_count"] == m.n_live == m.doc_count, (ctx, sc)
-    assert sc["hdr_token_count"] == sum(l for l, _ in m.docs.values()) == m.token_count, (ctx, sc)
-    assert sc["max_tf"] == max_tf, (ctx, sc["max_tf"], max_tf)
-    assert sc["bm_words"] == (n_docs + 4095) // 4096, (ctx, sc)
-    assert sc["dense_q8_stride"] == ((n_docs + 16383) & ~16383) + 16384, (ctx, sc)
-    assert sc["cap_post"] >= P and sc["algo_on"] == 3, (ctx, sc)
-    assert (sc["scanm_dens"], sc["outl_share"], sc["bm_share"]) == (0.05, 8, 1 << 30), (ctx, sc)
-    # ---- docs and CSR
-    assert len(img["doc_ids"]) == n_docs == len(img["doc_len"]), ctx
-    assert np.array_equal(img["doc_ids"][m.live], m.ord_ids[m.live]), ctx
-    want_len = np.array([m.docs[int(d)][0] if lv else 0 for d, lv in zip(m.ord_ids, m.live)], dtype=np.uint32)
-    assert np.array_equal(img["doc_len"][m.live], want_len[m.live]), ctx
-    off, row, doc, tf = flat_rows(img)
-    assert len(off) == T_ + 2 and off[0] == 0 and (np.diff(off) >= 0).all() and off[-1] == P == len(img["post_dt"]), ctx
-    same_row = row[1:] == row[:-1]
-    assert (np.diff(doc)[same_row] > 0).all(), (ctx, "ordinals of a row must ascend strictly")
-    assert (doc < n_docs).all() and m.live[doc].all(), (ctx, "a posting of a dead or unknown ordinal")
-    want_off = np.concatenate([[0, 0], np.cumsum([m.df[t] for t in range(1, T_ + 1)])])
-    assert np.array_equal(off, want_off), (ctx, np.flatnonzero(off != want_off)[:8])
-    want_doc = np.concatenate([m.ords[t] for t in range(1, T_ + 1)])
-    want_tf = np.concatenate([m.tfs[t] for t in range(1, T_ + 1)])
-    bad = np.flatnonzero((doc != want_doc) | (tf != want_tf))
-    assert not len(bad), (ctx, "canonical postings", bad[:8], row[bad[:8]])
-    # ---- impacts and per-term maxima, both ranking functions
-    for a in T.ALGOS:
-        post = img[("post", a)]
-        assert len(post) == P, (ctx, a)
-        assert np.array_equal(post["doc"].astype(np.int64), doc), (ctx, a)
-        want = np.concatenate([m.impacts(t, a) for t in range(1, T_ + 1)])
-        bad = np.flatnonzero(post["imp"] != want)
-        assert not len(bad), (ctx, ALGO_NAME[a], "impact bits", bad[:8], row[bad[:8]], post["imp"][bad[:4]], want[bad[:4]])
-        mx = img[("maximp", a)]
-        want_mx = np.array([0] + [m.maximp(t, a) for t in range(1, T_ + 1)] + [0], dtype=np.uint32)
-        bad = np.flatnonzero(mx != want_mx)
-        assert len(mx) == T_ + 2 and not len(bad), (ctx, ALGO_NAME[a], "maximp", bad[:8], mx[bad[:8]], want_mx[bad[:8]])
-    # ---- block-presence bitmaps and rank directories
-    words = sc["bm_words"]
-    bm_terms = img["bm_terms"].tolist()
-    assert bm_terms == m.bm_terms(n_docs, sc["bm_share"]), ctx
-    assert bm_terms == [t for t in range(1, T_ + 1) if m.df[t] > 0], ctx           # (with this share: every list)
-    blk = img["blkmap"].reshape(len(bm_terms), words)
-    rnk = img["bmrank"].reshape(len(bm_terms), words + 1)
-    for r, t in enumerate(bm_terms):
-        assert np.array_equal(blk[r], m.blkmap(t, words)), (ctx, "blkmap", m.terms[t - 1], blk[r], m.blkmap(t, words))
-        assert np.array_equal(rnk[r], m.bmrank(t, words)), (ctx, "bmrank", m.terms[t - 1], rnk[r], m.bmrank(t, words))
-    # ---- dense columns
-    dense = img["dense_terms"].tolist()
-    assert dense == m.dense_terms(n_docs, sc["scanm_dens"]), (ctx, dense)
-    nc = len(dense)
-    for a in T.ALGOS:
-        col = img[("dense_col", a)].reshape(nc, n_docs)
-        for c, t in enumerate(dense):
-            bad = np.flatnonzero(col[c] != m.dense_col(t, a, n_docs))
-            assert not len(bad), (ctx, ALGO_NAME[a], "dense_col", m.terms[t - 1], bad[:8])
-    # ---- byte columns (BM25): 0 where the doc lacks the term and in the padding; for a posting
-    # max(L, 1) <= q8 <= min(255, L + 1), L = ceil(255 imp / max) exactly
-    q8 = img["dense_q8"]
-    assert q8.shape == (nc, sc["dense_q8_stride"]), (ctx, q8.shape)
-    for c, t in enumerate(dense):
-        lo, hi = T.q8_bounds(m.impacts(t, T.BM25), m.maximp(t, T.BM25))
-        got = q8[c][m.ords[t]].astype(np.int64)
-        bad = np.flatnonzero((got < lo) | (got > hi))
-        assert not len(bad), (ctx, "dense_q8", m.terms[t - 1], bad[:8], got[bad[:8]], lo[bad[:8]], hi[bad[:8]])
-        rest = q8[c].copy()
-        rest[m.ords[t]] = 0
-        assert not rest.any(), (ctx, "dense_q8 cells without a posting", m.terms[t - 1], np.flatnonzero(rest)[:8])
-    # ---- TF-IDF caps and outlier lists
-    o_off, o_post = img["outl_off"].astype(np.int64), img["outl_post"]
-    assert len(o_off) == nc + 1 and len(img["outl_cap"]) == nc == len(img["outl_max"]), ctx
-    assert o_off[0] == sc["cap_post"] and (np.diff(o_off) >= 0).all() and len(o_post) == o_off[-1] - o_off[0], ctx
-    for c, t in enumerate(dense):
-        cap, ords, xb, cap_bits, max_bits = m.outliers(t, sc["outl_share"])
-        lst = o_post[o_off[c] - o_off[0]:o_off[c + 1] - o_off[0]]
-        who = (ctx, "outliers", m.terms[t - 1], cap)
-        assert np.array_equal(lst["doc"].astype(np.int64), ords), who
-        assert np.array_equal(lst["imp"], xb), (who, lst["imp"][:4], xb[:4])
-        assert int(img["outl_cap"][c]) == cap_bits and int(img["outl_max"][c]) == max_bits, \
-            (who, int(img["outl_cap"][c]), cap_bits, int(img["outl_max"][c]), max_bits)
-    return {"dense": dense, "bm_rows": len(bm_terms)}
-
-
-def canonical(img):
-    """per posting (term, doc id, tf, impact bits under both functions), and the per-term maxima: what a
-    refreshed and a freshly loaded index must agree on (ordinals and the dense set may differ)"""
-    _, row, doc, tf = flat_rows(img)
-    return (row, img["doc_ids"][doc], tf, img[("post", T.TF_IDF)]["imp"], img[("post", T.BM25)]["imp"],
-            img[("maximp", T.TF_IDF)], img[("maximp", T.BM25)])
+# the checker of one image, shared with the doc-shard image tests (tests/test_docshard_image.py) and run on
+# images made from the model by the CPU tier
+flat_rows, check_image, canonical = T.flat_rows, T.check_image, T.canonical
 
 
 class Walk:
