@@ -801,7 +801,14 @@ group_topk_take(uint64_t mine, uint64_t *s_top, uint32_t k, uint64_t *s_w, unsig
 	}
 }
 
-/* the k smallest of list[0 .. n), in order: emit(r, key) runs on thread 0 for the r-th; -> how many there are */
+/*
+ * The k smallest of list[0 .. n), in order: emit(r, key) runs on thread 0 for the r-th; -> how many there are.
+ * (k_wc_merge, k_rt_merge.)  Three selections of the same round structure stay kernels of their own, and the helper is
+ * not templated on a key type for them: k_sg_select works on ONE wavefront (no LDS, no barrier) with 128-bit keys;
+ * k_dv_merge on one wavefront with a cursor per part over lists that are already sorted -- it compares the parts'
+ * heads, it does not pass over the keys again every round; and k_px_select, whose loop this is statement for statement
+ * but for the early exit, measured 7-9 % slower through the helper on ranges of ~1500 keys (NOTES.md) and keeps its own.
+ */
 template <int GROUP, typename F>
 static __device__ __forceinline__ uint32_t
 group_topk_merge(const uint64_t *__restrict__ list, uint32_t n, uint32_t k, uint64_t *s_w, unsigned tid, F &&emit)

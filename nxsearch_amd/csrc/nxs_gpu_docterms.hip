@@ -31,8 +31,8 @@
  *                (nxs_ex_find) for w, tf and df.
  *
  * Device memory is docs x parts x k keys, never a list of hits; a batch whose partial lists would exceed
- * NXS_GPU_DOCTERMS_WS (64 MiB) is cut into passes of whole chunks.  The pass has a stream, grow-only workspace, pinned
- * staging and events of its own: beside batches and fuzzy passes in flight, none of their slots; blocking.
+ * NXS_GPU_DOCTERMS_WS (64 MiB) is cut into passes of whole chunks.  The pass has a side_t of its own (stream, grow-only
+ * workspace, pinned staging, events: nxs_gpu_int.h): beside batches and fuzzy passes in flight, none of their slots; blocking.
  * Nothing exists until the first call.  Under NXS_GPU_DOCTERMS=host the posting arrays are copied back and
  * the same lookups (nxs_dv_term) and a plain sort run on the host: the cross-check route.
  */
@@ -40,15 +40,10 @@
 #include "nxs_docterms.h"
 
 #define	DV_NONE		(~0ull)
+#define	DV_EVENTS	6
 
 struct dv_state_t {
-	hipStream_t	st;
-	void *		ws;
-	size_t		ws_len;
-	uint8_t *	pin;
-	size_t		pin_len;
-	hipEvent_t	ev[6];
-	bool		ev_ok;
+	side_t		side;
 	double		prof[NXSGPU_DOCTERMS_PROF];
 };
 
@@ -327,92 +322,11 @@ k_dv_merge(const uint64_t *__restrict__ partial, uint32_t np, uint32_t k,
 void
 dv_free(nxsgpu_index_t *ix)
 {
-	dv_state_t *dv = ix->dv;
-
-	if (!dv) {
-		return;
+	if (ix->dv) {
+		side_close(&ix->dv->side, true);
+		delete ix->dv;
+		ix->dv = NULL;
 	}
-	if (dv->st) {
-		(void)hipStreamSynchronize(dv->st);
-		(void)hipStreamDestroy(dv->st);
-	}
-	for (int i = 0; dv->ev_ok && i < 6; i++) {
-		(void)hipEventDestroy(dv->ev[i]);
-	}
-	(void)hipFree(dv->ws);
-	if (dv->pin) {
-		(void)hipHostFree(dv->pin);
-	}
-	delete dv;
-	ix->dv = NULL;
-}
-
-static int
-dv_prepare(nxsgpu_index_t *ix)
-{
-	dv_state_t *dv = ix->dv;
-
-	if (!dv) {
-		dv = new dv_state_t();
-		if (hipStreamCreateWithFlags(&dv->st, hipStreamNonBlocking) != hipSuccess) {
-			delete dv;
-			set_error("doc_terms: no stream");
-			return -1;
-		}
-		ix->dv = dv;
-	}
-	if (ix->profiling && !dv->ev_ok) {
-		int made = 0;
-
-		while (made < 6 && hipEventCreate(&dv->ev[made]) == hipSuccess) {
-			made++;
-		}
-		if (made < 6) {
-			while (made--) {
-				(void)hipEventDestroy(dv->ev[made]);
-			}
-			set_error("doc_terms: no events");
-			return -1;
-		}
-		dv->ev_ok = true;
-	}
-	return 0;
-}
-
-static int
-dv_room(dv_state_t *dv, size_t pin_need, size_t ws_need)
-{
-	if (dv->pin_len < pin_need) {
-		if (dv->pin) {
-			(void)hipHostFree(dv->pin);
-			dv->pin = NULL;
-			dv->pin_len = 0;
-		}
-		if (hipHostMalloc((void **)&dv->pin, pin_need, hipHostMallocDefault) != hipSuccess) {
-			set_error("hipHostMalloc(%zu) for the doc_terms staging failed", pin_need);
-			return -1;
-		}
-		dv->pin_len = pin_need;
-	}
-	if (dv->ws_len < ws_need) {
-		if (dv->ws) {
-			(void)hipFree(dv->ws);
-			dv->ws = NULL;
-			dv->ws_len = 0;
-		}
-		if (hipMalloc(&dv->ws, ws_need) != hipSuccess) {
-			set_error("hipMalloc(%zu) for the doc_terms workspace failed", ws_need);
-			return -1;
-		}
-		dv->ws_len = ws_need;
-	}
-	return 0;
-}
-
-static inline size_t
-dv_al(size_t n)
-{
-	return (n + 255) & ~(size_t)255;
 }
 
 /* the rows of unique doc u (ascending ordinals) into the rows of every caller's doc that has its ordinal */
@@ -468,7 +382,7 @@ dv_host(nxsgpu_index_t *ix, int algo, const uint64_t *doc_ids, uint32_t n, uint3
 	std::vector<uint64_t> h_ids(D), h_dt(P), h_blk(rows * ix->bm_words), ord_of(n);
 	std::vector<posting_t> h_post(P);
 	std::vector<uint32_t> h_rank(rows * (ix->bm_words + 1)), uniq;
-	hipStream_t st = ix->dv->st;
+	hipStream_t st = ix->dv->side.st;
 
 	if ((D && hipMemcpyAsync(h_ids.data(), ix->d_doc_ids, D * 8, hipMemcpyDeviceToHost, st) != hipSuccess) ||
 	    (P && hipMemcpyAsync(h_dt.data(), ix->d_post_dt, P * 8, hipMemcpyDeviceToHost, st) != hipSuccess) ||
@@ -572,12 +486,17 @@ nxsgpu_doc_terms(nxsgpu_index_t *ix, int algo, const uint64_t *doc_ids, uint32_t
 		set_error("hipSetDevice failed");
 		return -1;
 	}
-	if (dv_prepare(ix) != 0) {
-		return -1;
+	if (!ix->dv) {
+		ix->dv = new dv_state_t();
 	}
 	dv_state_t *dv = ix->dv;
-	hipStream_t st = dv->st;
-	const bool prof = ix->profiling && dv->ev_ok;
+	side_t *sd = &dv->side;
+
+	if (side_open(ix, sd, "doc_terms", DV_EVENTS, true) != 0) {
+		return -1;
+	}
+	hipStream_t st = sd->st;
+	const bool prof = ix->profiling && sd->ev_ok;
 
 	if (ix->cfg.docterms_host) {
 		return dv_host(ix, algo, doc_ids, n, mindf, k, term_ids, w, tf, df, counts, matches, found);
@@ -596,15 +515,15 @@ nxsgpu_doc_terms(nxsgpu_index_t *ix, int algo, const uint64_t *doc_ids, uint32_t
 	    std::max<uint64_t>(1, ix->cfg.docterms_ws / per_doc / NXS_DV_CHUNK) * NXS_DV_CHUNK);
 	const uint32_t pm = std::min(pass_docs, n);	/* unique docs of a pass at most */
 	/* workspace: doc ids | ordinals (u64) | bitmap terms | unique ordinals | rows | counts | matches | partial lists */
-	const size_t o_ord64 = dv_al((size_t)n * 8), o_bm = o_ord64 + dv_al((size_t)n * 8), o_uq = o_bm + dv_al((size_t)n_bm * 4 + 4);
-	const size_t o_dn = o_uq + dv_al((size_t)n * 4);
-	const size_t dn_rows = dv_al((size_t)pm * k * 4), dn_len = 4 * dn_rows + 2 * dv_al((size_t)pm * 4);
+	const size_t o_ord64 = al256((size_t)n * 8), o_bm = o_ord64 + al256((size_t)n * 8), o_uq = o_bm + al256((size_t)n_bm * 4 + 4);
+	const size_t o_dn = o_uq + al256((size_t)n * 4);
+	const size_t dn_rows = al256((size_t)pm * k * 4), dn_len = 4 * dn_rows + 2 * al256((size_t)pm * 4);
 	const size_t o_part = o_dn + dn_len, ws_need = o_part + (size_t)pm * per_doc + 512;
 
-	if (dv_room(dv, o_part, ws_need) != 0) {
+	if (side_room(sd, "doc_terms", o_part, ws_need) != 0) {
 		return -1;
 	}
-	uint8_t *h = dv->pin, *d = (uint8_t *)(((uintptr_t)dv->ws + 255) & ~(uintptr_t)255);
+	uint8_t *h = sd->pin, *d = (uint8_t *)(((uintptr_t)sd->ws + 255) & ~(uintptr_t)255);
 	std::vector<uint64_t> ord_of(n);
 	std::vector<uint32_t> uniq;
 
@@ -619,10 +538,10 @@ nxsgpu_doc_terms(nxsgpu_index_t *ix, int algo, const uint64_t *doc_ids, uint32_t
 		(void)hipStreamSynchronize(st);
 		return -1;
 	}
-	if (prof) (void)hipEventRecord(dv->ev[0], st);
+	if (prof) (void)hipEventRecord(sd->ev[0], st);
 	hipLaunchKernelGGL(k_dv_ord, dim3((n + 255) / 256), dim3(256), 0, st, (const uint64_t *)d, n, ix->d_doc_ids,
 	    ix->n_docs, (uint64_t *)(d + o_ord64));
-	if (prof) (void)hipEventRecord(dv->ev[1], st);
+	if (prof) (void)hipEventRecord(sd->ev[1], st);
 	if (hipGetLastError() != hipSuccess ||
 	    hipMemcpyAsync(h + o_ord64, d + o_ord64, (size_t)n * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
 	    hipStreamSynchronize(st) != hipSuccess) {
@@ -640,9 +559,7 @@ nxsgpu_doc_terms(nxsgpu_index_t *ix, int algo, const uint64_t *doc_ids, uint32_t
 	dv_unique(ord_of, uniq);
 	dv->prof[0] += 1;
 	if (prof) {
-		float ms = 0;
-		(void)hipEventElapsedTime(&ms, dv->ev[0], dv->ev[1]);
-		dv->prof[1] += ms;
+		dv->prof[1] += side_elapsed(sd, 0, 1);
 	}
 	const uint32_t nu = (uint32_t)uniq.size();
 	if (nu == 0 || T == 0) {
@@ -658,7 +575,7 @@ nxsgpu_doc_terms(nxsgpu_index_t *ix, int algo, const uint64_t *doc_ids, uint32_t
 	uint8_t *d_dn = d + o_dn, *h_dn = h + o_dn;
 	uint32_t *d_ids = (uint32_t *)d_dn, *d_tf = (uint32_t *)(d_dn + 2 * dn_rows), *d_df = (uint32_t *)(d_dn + 3 * dn_rows);
 	float *d_w = (float *)(d_dn + dn_rows);
-	uint32_t *d_counts = (uint32_t *)(d_dn + 4 * dn_rows), *d_matches = (uint32_t *)(d_dn + 4 * dn_rows + dv_al((size_t)pm * 4));
+	uint32_t *d_counts = (uint32_t *)(d_dn + 4 * dn_rows), *d_matches = (uint32_t *)(d_dn + 4 * dn_rows + al256((size_t)pm * 4));
 
 	for (uint32_t u0 = 0; u0 < nu; u0 += pass_docs) {
 		const uint32_t m = std::min(pass_docs, nu - u0);
@@ -669,15 +586,15 @@ nxsgpu_doc_terms(nxsgpu_index_t *ix, int algo, const uint64_t *doc_ids, uint32_t
 			(void)hipStreamSynchronize(st);
 			return -1;
 		}
-		if (prof) (void)hipEventRecord(dv->ev[2], st);
+		if (prof) (void)hipEventRecord(sd->ev[2], st);
 		hipLaunchKernelGGL(k_dv_scan, dim3(np, (m + NXS_DV_CHUNK - 1) / NXS_DV_CHUNK), dim3(WAVE),
 		    (size_t)NXS_DV_CHUNK * k * 8, st, ix->d_post_off, ix->d_post_dt, ix->d_post[algo], ix->d_blkmap, ix->d_bmrank,
 		    ix->bm_words, d_bm, n_bm, bm_mindf, T, d_ords, m, np, k, mindf, (uint64_t *)(d + o_part), d_matches);
-		if (prof) (void)hipEventRecord(dv->ev[3], st);
+		if (prof) (void)hipEventRecord(sd->ev[3], st);
 		hipLaunchKernelGGL(k_dv_merge, dim3(m), dim3(WAVE), 0, st, (const uint64_t *)(d + o_part), np, k, ix->d_post_off,
 		    ix->d_post_dt, ix->d_post[algo], ix->d_blkmap, ix->d_bmrank, ix->bm_words, d_bm, n_bm, d_ords, d_ids, d_w,
 		    d_tf, d_df, d_counts);
-		if (prof) (void)hipEventRecord(dv->ev[4], st);
+		if (prof) (void)hipEventRecord(sd->ev[4], st);
 		if (hipGetLastError() != hipSuccess) {
 			set_error("doc_terms kernel launch failed");
 			(void)hipStreamSynchronize(st);
@@ -689,17 +606,14 @@ nxsgpu_doc_terms(nxsgpu_index_t *ix, int algo, const uint64_t *doc_ids, uint32_t
 			return -1;
 		}
 		const uint32_t *s_counts = (const uint32_t *)(h_dn + 4 * dn_rows);
-		const uint32_t *s_matches = (const uint32_t *)(h_dn + 4 * dn_rows + dv_al((size_t)pm * 4));
+		const uint32_t *s_matches = (const uint32_t *)(h_dn + 4 * dn_rows + al256((size_t)pm * 4));
 
 		dv_scatter(ord_of, uniq, u0, m, k, (const uint32_t *)h_dn, (const float *)(h_dn + dn_rows),
 		    (const uint32_t *)(h_dn + 2 * dn_rows), (const uint32_t *)(h_dn + 3 * dn_rows), s_counts, s_matches,
 		    term_ids, w, tf, df, counts, matches);
 		if (prof) {
-			float ms = 0;
-			(void)hipEventElapsedTime(&ms, dv->ev[2], dv->ev[3]);
-			dv->prof[2] += ms;
-			(void)hipEventElapsedTime(&ms, dv->ev[3], dv->ev[4]);
-			dv->prof[3] += ms;
+			dv->prof[2] += side_elapsed(sd, 2, 3);
+			dv->prof[3] += side_elapsed(sd, 3, 4);
 		}
 		dv->prof[4] += 1;
 		dv->prof[5] += m;

@@ -19,8 +19,7 @@
  *                row-major (result, token); present cells are counted per wavefront (one atomic each).
  *                The lane's work is ex_lane(), host + device, so the same code can be run over host arrays.
  *
- * The pass has a stream, a grow-only workspace, pinned staging and events of its own (as nxsgpu_suggest and
- * nxsgpu_complete): it runs beside batches and fuzzy passes in flight, takes none of their slots, and is
+ * The pass has a side_t of its own (stream, grow-only workspace, pinned staging, events: nxs_gpu_int.h): it runs beside batches and fuzzy passes in flight, takes none of their slots, and is
  * blocking.  It is cut into chunks of at most cfg.explain_rows cells (NXS_GPU_EXPLAIN_ROWS; a chunk holds
  * whole result rows and at least one); a chunk is a contiguous run of the caller's results, so what comes
  * back is copied straight into the caller's arrays.  Nothing exists until the first call.
@@ -42,13 +41,7 @@ struct ex_blk_t {
 };
 
 struct ex_state_t {
-	hipStream_t	st;
-	void *		ws;
-	size_t		ws_len;
-	uint8_t *	pin;
-	size_t		pin_len;
-	hipEvent_t	ev[2];
-	bool		ev_ok;
+	side_t		side;
 	double		prof[NXSGPU_EXPLAIN_PROF];
 };
 
@@ -123,89 +116,11 @@ k_explain(const ex_blk_t *__restrict__ blks, const ex_tok_t *__restrict__ toks,
 void
 ex_free(nxsgpu_index_t *ix)
 {
-	ex_state_t *ex = ix->ex;
-
-	if (!ex) {
-		return;
+	if (ix->ex) {
+		side_close(&ix->ex->side, true);
+		delete ix->ex;
+		ix->ex = NULL;
 	}
-	if (ex->st) {
-		(void)hipStreamSynchronize(ex->st);
-		(void)hipStreamDestroy(ex->st);
-	}
-	for (int i = 0; ex->ev_ok && i < 2; i++) {
-		(void)hipEventDestroy(ex->ev[i]);
-	}
-	(void)hipFree(ex->ws);
-	if (ex->pin) {
-		(void)hipHostFree(ex->pin);
-	}
-	delete ex;
-	ix->ex = NULL;
-}
-
-static int
-ex_prepare(nxsgpu_index_t *ix)
-{
-	ex_state_t *ex = ix->ex;
-
-	if (!ex) {
-		ex = new ex_state_t();
-		if (hipStreamCreateWithFlags(&ex->st, hipStreamNonBlocking) != hipSuccess) {
-			delete ex;
-			set_error("explain: no stream");
-			return -1;
-		}
-		ix->ex = ex;
-	}
-	if (ix->profiling && !ex->ev_ok) {
-		if (hipEventCreate(&ex->ev[0]) != hipSuccess) {
-			set_error("explain: no events");
-			return -1;
-		}
-		if (hipEventCreate(&ex->ev[1]) != hipSuccess) {
-			(void)hipEventDestroy(ex->ev[0]);
-			set_error("explain: no events");
-			return -1;
-		}
-		ex->ev_ok = true;
-	}
-	return 0;
-}
-
-static int
-ex_room(ex_state_t *ex, size_t pin_need, size_t ws_need)
-{
-	if (ex->pin_len < pin_need) {
-		if (ex->pin) {
-			(void)hipHostFree(ex->pin);
-			ex->pin = NULL;
-			ex->pin_len = 0;
-		}
-		if (hipHostMalloc((void **)&ex->pin, pin_need, hipHostMallocDefault) != hipSuccess) {
-			set_error("hipHostMalloc(%zu) for the explain staging failed", pin_need);
-			return -1;
-		}
-		ex->pin_len = pin_need;
-	}
-	if (ex->ws_len < ws_need) {
-		if (ex->ws) {
-			(void)hipFree(ex->ws);
-			ex->ws = NULL;
-			ex->ws_len = 0;
-		}
-		if (hipMalloc(&ex->ws, ws_need) != hipSuccess) {
-			set_error("hipMalloc(%zu) for the explain workspace failed", ws_need);
-			return -1;
-		}
-		ex->ws_len = ws_need;
-	}
-	return 0;
-}
-
-static inline size_t
-ex_al(size_t n)
-{
-	return (n + 255) & ~(size_t)255;
 }
 
 /*
@@ -290,12 +205,17 @@ nxsgpu_explain(nxsgpu_index_t *ix, int algo, uint32_t n_queries,
 		set_error("hipSetDevice failed");
 		return -1;
 	}
-	if (ex_prepare(ix) != 0) {
-		return -1;
+	if (!ix->ex) {
+		ix->ex = new ex_state_t();
 	}
 	ex_state_t *ex = ix->ex;
-	hipStream_t st = ex->st;
-	const bool prof = ix->profiling && ex->ev_ok;
+	side_t *sd = &ex->side;
+
+	if (side_open(ix, sd, "explain", 2, true) != 0) {
+		return -1;
+	}
+	hipStream_t st = sd->st;
+	const bool prof = ix->profiling && sd->ev_ok;
 	const uint64_t max_cells = std::max<uint64_t>(ix->cfg.explain_rows, 1);
 
 	/* the token table: list bounds from the host's copy of the row offsets (an id outside the dictionary
@@ -337,17 +257,18 @@ nxsgpu_explain(nxsgpu_index_t *ix, int algo, uint32_t n_queries,
 		}
 		/* a chunk is one run of the caller's results, [r_first, r), and of its cells */
 		const uint64_t c_res = r - r_first;
-		const size_t up_blk = ex_al(blks.size() * sizeof(ex_blk_t));
-		const size_t up_tok = ex_al((size_t)n_tok * sizeof(ex_tok_t));
-		const size_t up_ids = ex_al((size_t)c_res * 8);
+		const size_t up_blk = al256(blks.size() * sizeof(ex_blk_t));
+		const size_t up_tok = al256((size_t)n_tok * sizeof(ex_tok_t));
+		const size_t up_ids = al256((size_t)c_res * 8);
 		const size_t up_len = up_blk + up_tok + up_ids;
-		const size_t dn_tf = ex_al((size_t)c_cells * 4), dn_imp = dn_tf, dn_found = ex_al((size_t)c_res), dn_cnt = 256;
+		const size_t dn_tf = al256((size_t)c_cells * 4), dn_imp = dn_tf, dn_found = al256((size_t)c_res), dn_cnt = 256;
 		const size_t dn_len = dn_tf + dn_imp + dn_found + dn_cnt;
 
-		if (ex_room(ex, up_len + dn_len, up_len + dn_len + 256) != 0) {
+		/* (exact staging: the token table is as long as the CALL's token lists, no chunk budget bounds it) */
+		if (side_room(sd, "explain", up_len + dn_len, up_len + dn_len + 256, true) != 0) {
 			return -1;
 		}
-		uint8_t *h = ex->pin, *d = (uint8_t *)(((uintptr_t)ex->ws + 255) & ~(uintptr_t)255);
+		uint8_t *h = sd->pin, *d = (uint8_t *)(((uintptr_t)sd->ws + 255) & ~(uintptr_t)255);
 		memcpy(h, blks.data(), blks.size() * sizeof(ex_blk_t));
 		memcpy(h + up_blk, toks.data(), (size_t)n_tok * sizeof(ex_tok_t));
 		memcpy(h + up_blk + up_tok, doc_ids + r_first, (size_t)c_res * 8);
@@ -359,13 +280,13 @@ nxsgpu_explain(nxsgpu_index_t *ix, int algo, uint32_t n_queries,
 			(void)hipStreamSynchronize(st);
 			return -1;
 		}
-		if (prof) (void)hipEventRecord(ex->ev[0], st);
+		if (prof) (void)hipEventRecord(sd->ev[0], st);
 		hipLaunchKernelGGL(k_explain, dim3((unsigned)blks.size()), dim3(WAVE), 0, st,
 		    (const ex_blk_t *)d, (const ex_tok_t *)(d + up_blk), (const uint64_t *)(d + up_blk + up_tok),
 		    ix->d_doc_ids, ix->n_docs, ix->d_post_dt, ix->d_post[algo], ix->d_blkmap, ix->d_bmrank, ix->bm_words,
 		    (uint32_t *)d_dn, (float *)(d_dn + dn_tf), d_dn + dn_tf + dn_imp,
 		    (unsigned long long *)(d_dn + dn_tf + dn_imp + dn_found));
-		if (prof) (void)hipEventRecord(ex->ev[1], st);
+		if (prof) (void)hipEventRecord(sd->ev[1], st);
 		if (hipGetLastError() != hipSuccess) {
 			set_error("explain kernel launch failed");
 			(void)hipStreamSynchronize(st);
@@ -381,9 +302,7 @@ nxsgpu_explain(nxsgpu_index_t *ix, int algo, uint32_t n_queries,
 		memcpy(found + (r_first - res_off[0]), h_dn + dn_tf + dn_imp, (size_t)c_res);
 		cell_done += c_cells;
 		if (prof) {
-			float ms = 0;
-			(void)hipEventElapsedTime(&ms, ex->ev[0], ex->ev[1]);
-			ex->prof[1] += ms;
+			ex->prof[1] += side_elapsed(sd, 0, 1);
 		}
 		ex->prof[2] += (double)c_cells;
 		ex->prof[3] += (double)*(const unsigned long long *)(h_dn + dn_tf + dn_imp + dn_found);

@@ -1235,24 +1235,14 @@ fuzzy_search(nxsgpu_index_t *ix, const uint8_t *tok_bytes, const uint32_t *tok_o
 struct sg_key_t { uint64_t hi, lo; };		/* d << 32 | ~df, term id */
 
 struct sg_state_t {
+	side_t		side;
 	bool		built;
 	uint64_t	built_gen;
 	uint32_t *	d_node;		/* [n_c] candidates, sorted by term length */
 	uint32_t *	d_sig;
 	uint8_t *	d_len;
 	uint32_t	n_c;
-	/* the host ranker's dictionary: every node with df > 0, any length */
-	std::vector<nxsgpu_bknode_t> h_nodes;
-	std::vector<uint8_t> h_bytes;
-	std::vector<const uint8_t *> h_terms;
-	std::vector<uint32_t> h_lens, h_dfs, h_ids;
-	hipStream_t	st;
-	void *		ws;
-	size_t		ws_len;
-	uint8_t *	pin;
-	size_t		pin_len;
-	hipEvent_t	ev[5];
-	bool		ev_ok;
+	dict_host_t	dict;		/* the host ranker's dictionary: every node with df > 0, any length */
 	double		prof[NXSGPU_SUGGEST_PROF];
 };
 
@@ -1448,20 +1438,10 @@ sg_free(nxsgpu_index_t *ix)
 	if (!sg) {
 		return;
 	}
-	if (sg->st) {
-		(void)hipStreamSynchronize(sg->st);
-		(void)hipStreamDestroy(sg->st);
-	}
-	for (int i = 0; sg->ev_ok && i < 5; i++) {
-		(void)hipEventDestroy(sg->ev[i]);
-	}
+	side_close(&sg->side, true);
 	(void)hipFree(sg->d_node);
 	(void)hipFree(sg->d_sig);
 	(void)hipFree(sg->d_len);
-	(void)hipFree(sg->ws);
-	if (sg->pin) {
-		(void)hipHostFree(sg->pin);
-	}
 	delete sg;
 	ix->sg = NULL;
 }
@@ -1470,27 +1450,13 @@ sg_free(nxsgpu_index_t *ix)
 static int
 sg_prepare(nxsgpu_index_t *ix)
 {
+	if (!ix->sg) {
+		ix->sg = new sg_state_t();
+	}
 	sg_state_t *sg = ix->sg;
 
-	if (!sg) {
-		sg = new sg_state_t();
-		if (hipStreamCreateWithFlags(&sg->st, hipStreamNonBlocking) != hipSuccess) {
-			delete sg;
-			set_error("suggest: no stream");
-			return -1;
-		}
-		ix->sg = sg;
-	}
-	if (ix->profiling && !sg->ev_ok) {
-		bool ok = true;
-		for (int i = 0; i < 5 && ok; i++) {
-			ok = hipEventCreate(&sg->ev[i]) == hipSuccess;
-		}
-		if (!ok) {
-			set_error("suggest: no events");
-			return -1;
-		}
-		sg->ev_ok = true;
+	if (side_open(ix, &sg->side, "suggest", 5, true) != 0) {
+		return -1;
 	}
 	if (sg->built && sg->built_gen == ix->sg_gen) {
 		return 0;
@@ -1502,44 +1468,20 @@ sg_prepare(nxsgpu_index_t *ix)
 	sg->d_node = sg->d_sig = NULL;
 	sg->d_len = NULL;
 	sg->n_c = 0;
-	sg->h_terms.clear();
-	sg->h_lens.clear();
-	sg->h_dfs.clear();
-	sg->h_ids.clear();
-
-	const uint32_t n = ix->n_bk;
-	sg->h_nodes.resize(n);
-	uint64_t blen = 0;
-	if (n && hipMemcpy(sg->h_nodes.data(), ix->d_bk, (size_t)n * sizeof(nxsgpu_bknode_t), hipMemcpyDeviceToHost) != hipSuccess) {
-		set_error("suggest: reading the BK image back failed");
+	if (dict_host_build(ix, sg->side.st, &sg->dict, "suggest") != 0) {
 		return -1;
 	}
-	for (uint32_t i = 0; i < n; i++) {
-		blen = std::max<uint64_t>(blen, (uint64_t)sg->h_nodes[i].str_off + sg->h_nodes[i].str_len);
-	}
-	sg->h_bytes.resize(blen + 16);
-	if (blen && hipMemcpy(sg->h_bytes.data(), ix->d_bk_bytes, blen, hipMemcpyDeviceToHost) != hipSuccess) {
-		set_error("suggest: reading the BK image back failed");
-		return -1;
-	}
-	/* df > 0: the live posting count of the CSR (what nxsgpu_index_df reports) */
-	auto df_of = [&](uint32_t i) -> uint32_t {
-		const uint32_t t = sg->h_nodes[i].term_id;
-		return (t >= 1 && t <= ix->n_terms) ? (uint32_t)(ix->h_post_off[(size_t)t + 1] - ix->h_post_off[t]) : 0;
+	/* the candidates: the dictionary's nodes (df > 0) of at most FZ_MAXLEN bytes, sorted by length */
+	const std::vector<nxsgpu_bknode_t> &nodes = sg->dict.h_nodes;
+	const uint32_t n = (uint32_t)nodes.size();
+	auto cand = [&](uint32_t i) -> bool {
+		return nodes[i].str_len <= FZ_MAXLEN && dict_df(ix->h_post_off.data(), ix->n_terms, nodes[i].term_id);
 	};
 	std::vector<uint32_t> start(FZ_MAXLEN + 2, 0), perm;
 	uint32_t n_c = 0;
 	for (uint32_t i = 0; i < n; i++) {
-		const uint32_t df = df_of(i);
-		if (!df) {
-			continue;
-		}
-		sg->h_terms.push_back(sg->h_bytes.data() + sg->h_nodes[i].str_off);
-		sg->h_lens.push_back(sg->h_nodes[i].str_len);
-		sg->h_dfs.push_back(df);
-		sg->h_ids.push_back(sg->h_nodes[i].term_id);
-		if (sg->h_nodes[i].str_len <= FZ_MAXLEN) {
-			start[sg->h_nodes[i].str_len + 1]++;
+		if (cand(i)) {
+			start[nodes[i].str_len + 1]++;
 			n_c++;
 		}
 	}
@@ -1548,21 +1490,21 @@ sg_prepare(nxsgpu_index_t *ix)
 	}
 	perm.resize(std::max<uint32_t>(n_c, 1));
 	for (uint32_t i = 0; i < n; i++) {
-		if (df_of(i) && sg->h_nodes[i].str_len <= FZ_MAXLEN) {
-			perm[start[sg->h_nodes[i].str_len]++] = i;
+		if (cand(i)) {
+			perm[start[nodes[i].str_len]++] = i;
 		}
 	}
 	if (n_c) {
 		if (hipMalloc(&sg->d_node, (size_t)n_c * 4) != hipSuccess ||
 		    hipMalloc(&sg->d_sig, (size_t)n_c * 4) != hipSuccess ||
 		    hipMalloc(&sg->d_len, (size_t)n_c + 16) != hipSuccess ||
-		    hipMemcpyAsync(sg->d_node, perm.data(), (size_t)n_c * 4, hipMemcpyHostToDevice, sg->st) != hipSuccess) {
+		    hipMemcpyAsync(sg->d_node, perm.data(), (size_t)n_c * 4, hipMemcpyHostToDevice, sg->side.st) != hipSuccess) {
 			set_error("suggest candidates: out of device memory");
 			return -1;
 		}
-		hipLaunchKernelGGL(k_fz_sigs, dim3((n_c + 255) / 256), dim3(256), 0, sg->st,
+		hipLaunchKernelGGL(k_fz_sigs, dim3((n_c + 255) / 256), dim3(256), 0, sg->side.st,
 		    ix->d_bk, ix->d_bk_bytes, sg->d_node, n_c, sg->d_sig, sg->d_len);
-		if (hipGetLastError() != hipSuccess || hipStreamSynchronize(sg->st) != hipSuccess) {
+		if (hipGetLastError() != hipSuccess || hipStreamSynchronize(sg->side.st) != hipSuccess) {
 			set_error("suggest candidates: k_fz_sigs failed");
 			return -1;
 		}
@@ -1605,38 +1547,18 @@ sg_pass(nxsgpu_index_t *ix, const uint8_t *tok_bytes, const uint32_t *tok_off, u
 	const size_t pin_need = up_bytes + ((blen + 16 + 15) & ~(size_t)15) + dn_bytes + 64;
 	const size_t need = ccap * sizeof(fz_item_t) + mcap * (sizeof(uint2) + sizeof(sg_key_t)) + dn_bytes +
 	    (size_t)n_tok * (256 * 8 + 8 + 4 + 4) + 64 + up_bytes + blen + 16 + 16 * 256;
-	hipStream_t st = sg->st;
-	const bool prof = ix->profiling && sg->ev_ok;
+	side_t *sd = &sg->side;
+	hipStream_t st = sd->st;
+	const bool prof = ix->profiling && sd->ev_ok;
 
-	if (sg->pin_len < pin_need) {
-		if (sg->pin) {
-			(void)hipHostFree(sg->pin);
-			sg->pin = NULL;
-			sg->pin_len = 0;
-		}
-		if (hipHostMalloc((void **)&sg->pin, pin_need + pin_need / 2, hipHostMallocDefault) != hipSuccess) {
-			set_error("hipHostMalloc(%zu) for the suggest staging failed", pin_need);
-			return -1;
-		}
-		sg->pin_len = pin_need + pin_need / 2;
+	if (side_room(sd, "suggest", pin_need, need) != 0) {
+		return -1;
 	}
-	if (sg->ws_len < need) {
-		if (sg->ws) {
-			(void)hipFree(sg->ws);
-			sg->ws = NULL;
-			sg->ws_len = 0;
-		}
-		if (hipMalloc(&sg->ws, need) != hipSuccess) {
-			set_error("hipMalloc(%zu) for the suggest workspace failed", need);
-			return -1;
-		}
-		sg->ws_len = need;
-	}
-	uint32_t *const up = (uint32_t *)sg->pin;
-	uint8_t *const h_dn = sg->pin + up_bytes + ((blen + 16 + 15) & ~(size_t)15);
+	uint32_t *const up = (uint32_t *)sd->pin;
+	uint8_t *const h_dn = sd->pin + up_bytes + ((blen + 16 + 15) & ~(size_t)15);
 	uint32_t *roff = up, *rank = roff + n_tok + 1, *len_off = rank + n_tok;
 
-	uint8_t *p = (uint8_t *)sg->ws;
+	uint8_t *p = (uint8_t *)sd->ws;
 	fz_item_t *d_cand = carve<fz_item_t>(p, ccap);
 	uint2 *d_match = carve<uint2>(p, mcap);
 	sg_key_t *d_keys = carve<sg_key_t>(p, mcap);
@@ -1673,18 +1595,18 @@ sg_pass(nxsgpu_index_t *ix, const uint8_t *tok_bytes, const uint32_t *tok_off, u
 			rank[i] = next[roff[i + 1] - roff[i]]++;
 		}
 	}
-	memcpy(sg->pin + up_bytes, tok_bytes + tok_off[0], blen);
-	if (hipMemcpyAsync(d_upb, sg->pin, up_bytes + blen, hipMemcpyHostToDevice, st) != hipSuccess ||
+	memcpy(sd->pin + up_bytes, tok_bytes + tok_off[0], blen);
+	if (hipMemcpyAsync(d_upb, sd->pin, up_bytes + blen, hipMemcpyHostToDevice, st) != hipSuccess ||
 	    hipMemsetAsync(d_dn, 0, dn_bytes, st) != hipSuccess ||
 	    hipMemsetAsync(d_tokf + n_tok, 0xff, 4 * sizeof(uint2), st) != hipSuccess) {
 		set_error("suggest upload failed");
 		return -1;
 	}
-	if (prof) (void)hipEventRecord(sg->ev[0], st);
+	if (prof) (void)hipEventRecord(sd->ev[0], st);
 	hipLaunchKernelGGL(k_bk_peq, dim3(n_tok), dim3(256), 0, st, d_bytes, d_off, n_tok, d_peq, d_tokf, d_rank);
 	hipLaunchKernelGGL(k_fz_filter, dim3((n_c + 255) / 256, gy), dim3(256), 0, st,
 	    sg->d_sig, sg->d_node, sg->d_len, n_c, d_tokf, d_len_off, d_cand, d_qcnt, (uint32_t)qcap, d_cnt + 2);
-	if (prof) (void)hipEventRecord(sg->ev[1], st);
+	if (prof) (void)hipEventRecord(sd->ev[1], st);
 	memset(&fa, 0, sizeof(fa));
 	fa.bk = ix->d_bk;
 	fa.bk_bytes = ix->d_bk_bytes;
@@ -1695,13 +1617,13 @@ sg_pass(nxsgpu_index_t *ix, const uint8_t *tok_bytes, const uint32_t *tok_off, u
 	fa.overflow = d_cnt + 2;
 	hipLaunchKernelGGL(k_sg_dist, dim3(8, FZ_NQ), dim3(1024), 0, st, fa, d_cand, d_qcnt, (uint32_t)qcap, maxdist,
 	    d_matches, d_match, d_cnt + 1, (uint32_t)mcap);
-	if (prof) (void)hipEventRecord(sg->ev[2], st);
+	if (prof) (void)hipEventRecord(sd->ev[2], st);
 	hipLaunchKernelGGL(k_sg_scan, dim3(1), dim3(1024), 0, st, d_matches, n_tok, d_segoff, d_fill);
 	hipLaunchKernelGGL(k_sg_scatter, dim3(512), dim3(256), 0, st, ix->d_bk, ix->d_post_off, ix->n_terms,
 	    d_match, d_cnt + 1, (uint32_t)mcap, d_segoff, d_fill, d_keys);
-	if (prof) (void)hipEventRecord(sg->ev[3], st);
+	if (prof) (void)hipEventRecord(sd->ev[3], st);
 	hipLaunchKernelGGL(k_sg_select, dim3(n_tok), dim3(64), 0, st, d_keys, d_segoff, (uint32_t)mcap, k, d_ids, d_dist, d_df, d_counts);
-	if (prof) (void)hipEventRecord(sg->ev[4], st);
+	if (prof) (void)hipEventRecord(sd->ev[4], st);
 	if (hipGetLastError() != hipSuccess) {
 		set_error("suggest kernel launch failed");
 		(void)hipStreamSynchronize(st);
@@ -1718,13 +1640,10 @@ sg_pass(nxsgpu_index_t *ix, const uint8_t *tok_bytes, const uint32_t *tok_off, u
 	const uint32_t *h_cnt = h_matches + n_tok, *h_qcnt = h_cnt + 4;
 	const uint8_t *h_dist = (const uint8_t *)(h_qcnt + FZ_NQ * FZ_CSTRIDE);
 	if (prof) {
-		float ms = 0;
 		sg->prof[0] += 1;
-		(void)hipEventElapsedTime(&ms, sg->ev[0], sg->ev[4]);
-		sg->prof[1] += ms;
+		sg->prof[1] += side_elapsed(sd, 0, 4);
 		for (int i = 0; i < 4; i++) {
-			(void)hipEventElapsedTime(&ms, sg->ev[i], sg->ev[i + 1]);
-			sg->prof[2 + i] += ms;
+			sg->prof[2 + i] += side_elapsed(sd, i, i + 1);
 		}
 	}
 	if (h_cnt[2]) {
@@ -1781,8 +1700,8 @@ nxsgpu_suggest(nxsgpu_index_t *ix, const uint8_t *tok_bytes, const uint32_t *tok
 		const uint32_t m = tok_off[i + 1] - tok_off[i];
 		if (ix->cfg.suggest_host || m > NXS_MYERS_MAXPAT) {
 #if !defined(__HIP_DEVICE_COMPILE__)	/* (nxs_lev.h keeps its host functions out of the device pass) */
-			nxs_suggest_rank(sg->h_terms.data(), sg->h_lens.data(), sg->h_dfs.data(), sg->h_ids.data(),
-			    sg->h_terms.size(), tok_bytes + tok_off[i], m, maxdist, k, term_ids + (size_t)i * k,
+			nxs_suggest_rank(sg->dict.h_terms.data(), sg->dict.h_lens.data(), sg->dict.h_dfs.data(),
+			    sg->dict.h_ids.data(), sg->dict.h_terms.size(), tok_bytes + tok_off[i], m, maxdist, k, term_ids + (size_t)i * k,
 			    dist + (size_t)i * k, df + (size_t)i * k, &counts[i], &matches[i]);
 #endif
 			sg->prof[8] += 1;

@@ -39,6 +39,8 @@
  *  nxs_gpu_related.hip    related terms of a query's matches: the doc sets of a group of plans as bits (k_rt_mask: k_count_tile's
  *                         body), one pass over the posting array that meets every list with them (k_rt_scan), a top-k
  *                         per plan and part (k_rt_select), the parts merged (k_rt_merge); nxs_related.h
+ *  nxs_gpu_side.hip       host only: what the six blocking side passes above share -- stream, workspace, staging and
+ *                         events (side_t), the host rankers' dictionary, the term-list download block
  *  nxs_gpu_plan.hip       host only: query classes, the work list (build_worklist) and
  *                         the layout of a batch's arrays (batch_layout)
  *  nxs_gpu_search.hip     kernel dispatch, blocking search, batches in flight
@@ -70,6 +72,7 @@
 
 #include "nxs_gpu.h"
 #include "nxs_lev.h"
+#include "nxs_side.h"
 
 #define	WAVE		64
 #ifndef TILE_W
@@ -659,6 +662,72 @@ int	bk_aux_build(nxsgpu_index_t *ix, const nxsgpu_bknode_t *nodes, uint32_t n);
 
 void	sg_free(nxsgpu_index_t *ix);		/* everything nxsgpu_suggest has built (index destroy) */
 
+/* ---- nxs_gpu_side.hip ---- */
+/*
+ * What every blocking side pass (suggest, complete, wildcard, explain, doc terms, related) owns beside its own
+ * data: a non-blocking stream, a grow-only device workspace, grow-only pinned staging and, once profiling is on,
+ * its events.  Zero-initialised with the pass's state; nothing exists until side_open / side_room make it.
+ */
+#define	SIDE_EVENTS	6		/* the largest user's (doc terms) */
+struct side_t {
+	hipStream_t	st;
+	void *		ws;
+	size_t		ws_len;
+	uint8_t *	pin;
+	size_t		pin_len;
+	hipEvent_t	ev[SIDE_EVENTS];
+	int		n_ev;
+	bool		ev_ok;		/* ev[0 .. n_ev) exist: the pass records them while ix->profiling is on */
+};
+/* the stream (own_stream, unless it exists) and, with profiling on -- it may be switched on between two calls --,
+ * the n_events events unless they exist: all of them or none.  0 / -1 ("<what>: no stream", "<what>: no events") */
+int	side_open(nxsgpu_index_t *ix, side_t *s, const char *what, int n_events, bool own_stream);
+/* at least pin_need bytes of staging and ws_need bytes of workspace; contents are not kept.  Staging grows to half
+ * again what is asked for (exact_pin: to just that), the workspace to just that.  0 / -1 */
+int	side_room(side_t *s, const char *what, size_t pin_need, size_t ws_need, bool exact_pin = false);
+/* milliseconds between events a and b of a finished pass */
+double	side_elapsed(const side_t *s, int a, int b);
+/* waits for the stream (own_stream: and destroys it), destroys the events, frees both buffers */
+void	side_close(side_t *s, bool own_stream);
+/* dict (nxs_side.h) for the index as it is now: the BK image read back on `st` (blocking), the df filter.  0 / -1 */
+int	dict_host_build(nxsgpu_index_t *ix, hipStream_t st, dict_host_t *dict, const char *what);
+double	now_ms(void);			/* monotonic clock */
+
+static inline size_t
+al256(size_t n)
+{
+	return (n + 255) & ~(size_t)255;
+}
+
+/*
+ * The block a term-list pass (complete, wildcard) brings back for n inputs, in its workspace and in its staging:
+ * term ids [n][k] | df [n][k] | counts [n] | matches [n], tl_bytes() long.
+ */
+struct tl_block_t { uint32_t *ids, *df, *counts, *matches; };
+static inline size_t
+tl_bytes(uint32_t n, uint32_t k)
+{
+	return ((((size_t)n * k + n) * 2) * 4 + 15) & ~(size_t)15;
+}
+static inline tl_block_t
+tl_layout(uint8_t *base, uint32_t n, uint32_t k)
+{
+	tl_block_t b;
+
+	b.ids = (uint32_t *)base;
+	b.df = b.ids + (size_t)n * k;
+	b.counts = b.df + (size_t)n * k;
+	b.matches = b.counts + n;
+	return b;
+}
+/* the staged block into the caller's arrays */
+void	tl_copy_out(const uint8_t *h_block, uint32_t n, uint32_t k, uint32_t *term_ids, uint32_t *df, uint32_t *counts,
+	    uint32_t *matches);
+/* how both calls begin: k in 1..k_max, n and the bytes within limits, the device set, the outputs cleared.
+ * 0: go on, 1: nothing to do (n == 0), -1: error ("<fn>: k is 1..<k_max>", "<fn>: too many <things>") */
+int	tl_enter(nxsgpu_index_t *ix, const char *fn, const char *things, uint32_t k, uint32_t k_max, const uint32_t *off,
+	    uint32_t n, uint32_t *term_ids, uint32_t *df, uint32_t *counts, uint32_t *matches);
+
 /* ---- nxs_gpu_prefix.hip ---- */
 /*
  * The live terms in byte order (the header of nxs_gpu_prefix.hip), built by the first call that needs them and
@@ -666,25 +735,16 @@ void	sg_free(nxsgpu_index_t *ix);		/* everything nxsgpu_suggest has built (index
  * blocking and run on the state's stream, one after the other.
  */
 struct px_state_t {
+	side_t		side;
 	bool		built;
 	uint64_t	built_gen;
 	uint32_t *	d_node;		/* [n_e] live nodes in byte order of their terms */
 	uint64_t *	d_key;		/* [n_e] ~df << 32 | term id of entry i */
 	uint32_t	n_e;
-	/* the host rankers' dictionary (NXS_GPU_COMPLETE=host, NXS_GPU_WILDCARD=host only): every node with df > 0 */
+	/* the host rankers' dictionary (NXS_GPU_COMPLETE=host, NXS_GPU_WILDCARD=host only) */
 	bool		h_built;
 	uint64_t	h_gen;
-	std::vector<nxsgpu_bknode_t> h_nodes;
-	std::vector<uint8_t> h_bytes;
-	std::vector<const uint8_t *> h_terms;
-	std::vector<uint32_t> h_lens, h_dfs, h_ids;
-	hipStream_t	st;
-	void *		ws;
-	size_t		ws_len;
-	uint8_t *	pin;
-	size_t		pin_len;
-	hipEvent_t	ev[3];
-	bool		ev_ok;
+	dict_host_t	dict;
 	double		prof[NXSGPU_COMPLETE_PROF];
 	uint64_t	builds;		/* of the order or the host copy, since the index was created */
 };

@@ -25,9 +25,9 @@
  *                wavefront, so the range is spread over four wavefronts here.  (Chosen from that count,
  *                not from a measurement: NOTES.md.)
  *
- * The pass has a stream, workspace, pinned staging and events of its own: one upload, the two kernels,
- * one copy back; blocking.  Under NXS_GPU_COMPLETE=host every prefix takes the host ranker
- * (nxs_complete.h) over a host copy of the BK image: the cross-check route.
+ * The pass has a side_t of its own (stream, workspace, pinned staging, events: nxs_gpu_int.h): one upload,
+ * the two kernels, one copy back; blocking.  Under NXS_GPU_COMPLETE=host every prefix takes the host ranker
+ * (nxs_complete.h) over the host dictionary (dict_host_build): the cross-check route.
  */
 #include "nxs_gpu_int.h"
 #include "nxs_complete.h"
@@ -227,30 +227,11 @@ px_free(nxsgpu_index_t *ix)
 	if (!px) {
 		return;
 	}
-	if (px->st) {
-		(void)hipStreamSynchronize(px->st);
-		(void)hipStreamDestroy(px->st);
-	}
-	for (int i = 0; px->ev_ok && i < 3; i++) {
-		(void)hipEventDestroy(px->ev[i]);
-	}
+	side_close(&px->side, true);
 	(void)hipFree(px->d_node);
 	(void)hipFree(px->d_key);
-	(void)hipFree(px->ws);
-	if (px->pin) {
-		(void)hipHostFree(px->pin);
-	}
 	delete px;
 	ix->px = NULL;
-}
-
-static double
-px_now_ms(void)
-{
-	struct timespec ts;
-
-	clock_gettime(CLOCK_MONOTONIC, &ts);
-	return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
 }
 
 /* the order of the index's current generation, on the device */
@@ -259,7 +240,7 @@ px_build_order(nxsgpu_index_t *ix)
 {
 	px_state_t *px = ix->px;
 	const uint32_t n = ix->n_bk;
-	const double t0 = px_now_ms();
+	const double t0 = now_ms();
 	uint32_t *d_node[2] = { NULL, NULL }, *d_cnt = NULL, h_cnt[2] = { 0, 0 };
 	uint64_t *d_keys[2] = { NULL, NULL };
 	void *d_tmp = NULL;
@@ -277,12 +258,12 @@ px_build_order(nxsgpu_index_t *ix)
 	if (n) {
 		HIP_TRY(hipMalloc(&d_node[0], (size_t)n * 4));
 		HIP_TRY(hipMalloc(&d_cnt, 8));
-		HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, px->st));
-		hipLaunchKernelGGL(k_px_live, dim3((n + 255) / 256), dim3(256), 0, px->st,
+		HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, px->side.st));
+		hipLaunchKernelGGL(k_px_live, dim3((n + 255) / 256), dim3(256), 0, px->side.st,
 		    ix->d_bk, n, ix->d_post_off, ix->n_terms, d_node[0], d_cnt);
 		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpyAsync(h_cnt, d_cnt, 8, hipMemcpyDeviceToHost, px->st));
-		HIP_TRY(hipStreamSynchronize(px->st));
+		HIP_TRY(hipMemcpyAsync(h_cnt, d_cnt, 8, hipMemcpyDeviceToHost, px->side.st));
+		HIP_TRY(hipStreamSynchronize(px->side.st));
 	}
 	n_e = std::min(h_cnt[0], n);
 	if (n_e) {
@@ -292,23 +273,23 @@ px_build_order(nxsgpu_index_t *ix)
 		HIP_TRY(hipMalloc(&d_keys[0], (size_t)n_e * 8));
 		HIP_TRY(hipMalloc(&d_keys[1], (size_t)n_e * 8));
 		HIP_TRY(rocprim::radix_sort_pairs(NULL, tmp_bytes, d_keys[0], d_keys[1], d_node[0], d_node[1],
-		    (size_t)n_e, 0, 64, px->st));
+		    (size_t)n_e, 0, 64, px->side.st));
 		HIP_TRY(hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 8));
 		/* LSD over the chunks: the sort is stable, so after the pass on chunk c the entries are in order
 		 * of their bytes from 8 c on */
 		for (uint32_t c = chunks; c-- > 0; ) {
-			hipLaunchKernelGGL(k_px_keys, dim3(grid), dim3(256), 0, px->st,
+			hipLaunchKernelGGL(k_px_keys, dim3(grid), dim3(256), 0, px->side.st,
 			    ix->d_bk, ix->d_bk_bytes, d_node[cur], n_e, c, d_keys[0]);
 			HIP_TRY(hipGetLastError());
 			HIP_TRY(rocprim::radix_sort_pairs(d_tmp, tmp_bytes, d_keys[0], d_keys[1], d_node[cur], d_node[cur ^ 1],
-			    (size_t)n_e, 0, 64, px->st));
+			    (size_t)n_e, 0, 64, px->side.st));
 			cur ^= 1;
 		}
 		/* (d_keys[0] becomes the selection keys: it is kept) */
-		hipLaunchKernelGGL(k_px_pairs, dim3(grid), dim3(256), 0, px->st,
+		hipLaunchKernelGGL(k_px_pairs, dim3(grid), dim3(256), 0, px->side.st,
 		    ix->d_bk, ix->d_post_off, ix->n_terms, d_node[cur], n_e, d_keys[0]);
 		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipStreamSynchronize(px->st));
+		HIP_TRY(hipStreamSynchronize(px->side.st));
 		px->d_node = d_node[cur];
 		px->d_key = d_keys[0];
 		d_node[cur] = NULL;
@@ -317,14 +298,14 @@ px_build_order(nxsgpu_index_t *ix)
 	px->n_e = n_e;
 	px->built = true;
 	px->built_gen = ix->px_gen;
-	px->prof[4] = px_now_ms() - t0;
+	px->prof[4] = now_ms() - t0;
 	px->prof[5] = n_e;
 	px->prof[7] += 1;
 	px->builds++;
 	ret = 0;
 fail:
 	if (ret != 0) {
-		(void)hipStreamSynchronize(px->st);
+		(void)hipStreamSynchronize(px->side.st);
 	}
 	(void)hipFree(d_node[0]);
 	(void)hipFree(d_node[1]);
@@ -335,51 +316,21 @@ fail:
 	return ret;
 }
 
-/* the host ranker's dictionary of the index's current generation: a copy of the BK image */
+/* the host rankers' dictionary of the index's current generation */
 static int
 px_build_host(nxsgpu_index_t *ix)
 {
 	px_state_t *px = ix->px;
-	const uint32_t n = ix->n_bk;
-	const double t0 = px_now_ms();
-	uint64_t blen = 0;
+	const double t0 = now_ms();
 
 	px->h_built = false;
-	px->h_terms.clear();
-	px->h_lens.clear();
-	px->h_dfs.clear();
-	px->h_ids.clear();
-	px->h_nodes.resize(n);
-	if (n && (hipMemcpyAsync(px->h_nodes.data(), ix->d_bk, (size_t)n * sizeof(nxsgpu_bknode_t), hipMemcpyDeviceToHost, px->st) != hipSuccess ||
-	    hipStreamSynchronize(px->st) != hipSuccess)) {
-		set_error("complete: reading the BK image back failed");
+	if (dict_host_build(ix, px->side.st, &px->dict, "complete") != 0) {
 		return -1;
-	}
-	for (uint32_t i = 0; i < n; i++) {
-		blen = std::max<uint64_t>(blen, (uint64_t)px->h_nodes[i].str_off + px->h_nodes[i].str_len);
-	}
-	px->h_bytes.resize(blen + 16);
-	if (blen && (hipMemcpyAsync(px->h_bytes.data(), ix->d_bk_bytes, blen, hipMemcpyDeviceToHost, px->st) != hipSuccess ||
-	    hipStreamSynchronize(px->st) != hipSuccess)) {
-		set_error("complete: reading the BK image back failed");
-		return -1;
-	}
-	for (uint32_t i = 0; i < n; i++) {
-		const uint32_t t = px->h_nodes[i].term_id;
-		const uint32_t df = (t >= 1 && t <= ix->n_terms) ? (uint32_t)(ix->h_post_off[(size_t)t + 1] - ix->h_post_off[t]) : 0;
-
-		if (!df) {
-			continue;
-		}
-		px->h_terms.push_back(px->h_bytes.data() + px->h_nodes[i].str_off);
-		px->h_lens.push_back(px->h_nodes[i].str_len);
-		px->h_dfs.push_back(df);
-		px->h_ids.push_back(t);
 	}
 	px->h_built = true;
 	px->h_gen = ix->px_gen;
-	px->prof[4] = px_now_ms() - t0;
-	px->prof[5] = (double)px->h_terms.size();
+	px->prof[4] = now_ms() - t0;
+	px->prof[5] = (double)px->dict.h_terms.size();
 	px->prof[7] += 1;
 	px->builds++;
 	return 0;
@@ -389,27 +340,13 @@ px_build_host(nxsgpu_index_t *ix)
 int
 px_prepare(nxsgpu_index_t *ix, bool host)
 {
+	if (!ix->px) {
+		ix->px = new px_state_t();
+	}
 	px_state_t *px = ix->px;
 
-	if (!px) {
-		px = new px_state_t();
-		if (hipStreamCreateWithFlags(&px->st, hipStreamNonBlocking) != hipSuccess) {
-			delete px;
-			set_error("complete: no stream");
-			return -1;
-		}
-		ix->px = px;
-	}
-	if (ix->profiling && !px->ev_ok) {
-		bool ok = true;
-		for (int i = 0; i < 3 && ok; i++) {
-			ok = hipEventCreate(&px->ev[i]) == hipSuccess;
-		}
-		if (!ok) {
-			set_error("complete: no events");
-			return -1;
-		}
-		px->ev_ok = true;
+	if (side_open(ix, &px->side, "complete", 3, true) != 0) {
+		return -1;
 	}
 	if (host) {
 		return px->h_built && px->h_gen == ix->px_gen ? 0 : px_build_host(ix);
@@ -423,64 +360,41 @@ px_pass(nxsgpu_index_t *ix, const uint8_t *bytes, const uint32_t *off, uint32_t 
     uint32_t *o_ids, uint32_t *o_df, uint32_t *o_counts, uint32_t *o_matches)
 {
 	px_state_t *px = ix->px;
+	side_t *sd = &px->side;
 	const uint32_t blen = off[n] - off[0];
-	const size_t rows = (size_t)n * k;
-	/* up: offsets | bytes; down: term ids | df | counts | matches */
+	/* up: offsets | bytes; down: the term-list block */
 	const size_t up_bytes = (((size_t)n + 1) * 4 + blen + 16 + 15) & ~(size_t)15;
-	const size_t dn_bytes = ((rows * 2 + (size_t)n * 2) * 4 + 15) & ~(size_t)15;
-	const size_t pin_need = up_bytes + dn_bytes;
-	const size_t need = up_bytes + dn_bytes + (size_t)n * sizeof(uint2) + 4 * 256;
-	hipStream_t st = px->st;
-	const bool prof = ix->profiling && px->ev_ok;
+	const size_t dn_bytes = tl_bytes(n, k);
+	hipStream_t st = sd->st;
+	const bool prof = ix->profiling && sd->ev_ok;
 
-	if (px->pin_len < pin_need) {
-		if (px->pin) {
-			(void)hipHostFree(px->pin);
-			px->pin = NULL;
-			px->pin_len = 0;
-		}
-		if (hipHostMalloc((void **)&px->pin, pin_need + pin_need / 2, hipHostMallocDefault) != hipSuccess) {
-			set_error("hipHostMalloc(%zu) for the complete staging failed", pin_need);
-			return -1;
-		}
-		px->pin_len = pin_need + pin_need / 2;
+	if (side_room(sd, "complete", up_bytes + dn_bytes, up_bytes + dn_bytes + (size_t)n * sizeof(uint2) + 4 * 256) != 0) {
+		return -1;
 	}
-	if (px->ws_len < need) {
-		if (px->ws) {
-			(void)hipFree(px->ws);
-			px->ws = NULL;
-			px->ws_len = 0;
-		}
-		if (hipMalloc(&px->ws, need) != hipSuccess) {
-			set_error("hipMalloc(%zu) for the complete workspace failed", need);
-			return -1;
-		}
-		px->ws_len = need;
-	}
-	uint32_t *const h_off = (uint32_t *)px->pin;
-	uint8_t *const h_dn = px->pin + up_bytes;
-	uint8_t *p = (uint8_t *)px->ws;
+	uint32_t *const h_off = (uint32_t *)sd->pin;
+	uint8_t *const h_dn = sd->pin + up_bytes;
+	uint8_t *p = (uint8_t *)sd->ws;
 	uint8_t *d_up = carve<uint8_t>(p, up_bytes);
 	uint8_t *d_dn = carve<uint8_t>(p, dn_bytes);
 	uint2 *d_range = carve<uint2>(p, n);
 	uint32_t *d_off = (uint32_t *)d_up;
 	uint8_t *d_bytes = d_up + ((size_t)n + 1) * 4;
-	uint32_t *d_ids = (uint32_t *)d_dn, *d_df = d_ids + rows, *d_counts = d_df + rows, *d_matches = d_counts + n;
+	const tl_block_t d = tl_layout(d_dn, n, k);
 
 	for (uint32_t i = 0; i <= n; i++) {
 		h_off[i] = off[i] - off[0];
 	}
-	memcpy(px->pin + ((size_t)n + 1) * 4, bytes + off[0], blen);
-	if (hipMemcpyAsync(d_up, px->pin, up_bytes, hipMemcpyHostToDevice, st) != hipSuccess ||
+	memcpy(sd->pin + ((size_t)n + 1) * 4, bytes + off[0], blen);
+	if (hipMemcpyAsync(d_up, sd->pin, up_bytes, hipMemcpyHostToDevice, st) != hipSuccess ||
 	    hipMemsetAsync(d_dn, 0, dn_bytes, st) != hipSuccess) {
 		set_error("complete upload failed");
 		return -1;
 	}
-	if (prof) (void)hipEventRecord(px->ev[0], st);
-	px_launch_range(ix, st, d_bytes, d_off, n, d_range, d_matches);
-	if (prof) (void)hipEventRecord(px->ev[1], st);
-	hipLaunchKernelGGL(k_px_select, dim3(n), dim3(PX_GROUP), 0, st, px->d_key, d_range, k, d_ids, d_df, d_counts);
-	if (prof) (void)hipEventRecord(px->ev[2], st);
+	if (prof) (void)hipEventRecord(sd->ev[0], st);
+	px_launch_range(ix, st, d_bytes, d_off, n, d_range, d.matches);
+	if (prof) (void)hipEventRecord(sd->ev[1], st);
+	hipLaunchKernelGGL(k_px_select, dim3(n), dim3(PX_GROUP), 0, st, px->d_key, d_range, k, d.ids, d.df, d.counts);
+	if (prof) (void)hipEventRecord(sd->ev[2], st);
 	if (hipGetLastError() != hipSuccess) {
 		set_error("complete kernel launch failed");
 		(void)hipStreamSynchronize(st);
@@ -491,21 +405,13 @@ px_pass(nxsgpu_index_t *ix, const uint8_t *bytes, const uint32_t *off, uint32_t 
 		set_error("complete pass failed: %s", hipGetErrorString(hipGetLastError()));
 		return -1;
 	}
-	const uint32_t *h_ids = (const uint32_t *)h_dn, *h_df = h_ids + rows, *h_counts = h_df + rows, *h_matches = h_counts + n;
 	if (prof) {
-		float ms = 0;
 		px->prof[0] += 1;
-		(void)hipEventElapsedTime(&ms, px->ev[0], px->ev[2]);
-		px->prof[1] += ms;
-		(void)hipEventElapsedTime(&ms, px->ev[0], px->ev[1]);
-		px->prof[2] += ms;
-		(void)hipEventElapsedTime(&ms, px->ev[1], px->ev[2]);
-		px->prof[3] += ms;
+		px->prof[1] += side_elapsed(sd, 0, 2);
+		px->prof[2] += side_elapsed(sd, 0, 1);
+		px->prof[3] += side_elapsed(sd, 1, 2);
 	}
-	memcpy(o_ids, h_ids, rows * 4);
-	memcpy(o_df, h_df, rows * 4);
-	memcpy(o_counts, h_counts, (size_t)n * 4);
-	memcpy(o_matches, h_matches, (size_t)n * 4);
+	tl_copy_out(h_dn, n, k, o_ids, o_df, o_counts, o_matches);
 	return 0;
 }
 
@@ -513,34 +419,22 @@ extern "C" int
 nxsgpu_complete(nxsgpu_index_t *ix, const uint8_t *bytes, const uint32_t *off, uint32_t n, uint32_t k,
     uint32_t *term_ids, uint32_t *df, uint32_t *counts, uint32_t *matches)
 {
-	if (k < 1 || k > NXS_COMPLETE_MAX) {
-		set_error("nxsgpu_complete: k is 1..%d", NXS_COMPLETE_MAX);
-		return -1;
-	}
-	if (n == 0) {
-		return 0;
-	}
-	if (n > (1u << 24) || off[n] - off[0] > (1u << 30)) {
-		set_error("nxsgpu_complete: too many prefixes");
-		return -1;
-	}
-	if (hipSetDevice(ix->device) != hipSuccess) {
-		set_error("hipSetDevice failed");
-		return -1;
+	const int go = tl_enter(ix, "nxsgpu_complete", "prefixes", k, NXS_COMPLETE_MAX, off, n, term_ids, df, counts, matches);
+
+	if (go != 0) {
+		return go < 0 ? -1 : 0;
 	}
 	if (px_prepare(ix, ix->cfg.complete_host) != 0) {
 		return -1;
 	}
 	px_state_t *px = ix->px;
 
-	memset(term_ids, 0, (size_t)n * k * 4);
-	memset(df, 0, (size_t)n * k * 4);
-	memset(counts, 0, (size_t)n * 4);
-	memset(matches, 0, (size_t)n * 4);
 	if (ix->cfg.complete_host) {
+		const dict_host_t &dc = px->dict;
+
 		for (uint32_t i = 0; i < n; i++) {
-			nxs_complete_rank(px->h_terms.data(), px->h_lens.data(), px->h_dfs.data(), px->h_ids.data(),
-			    px->h_terms.size(), bytes + off[i], off[i + 1] - off[i], k, term_ids + (size_t)i * k,
+			nxs_complete_rank(dc.h_terms.data(), dc.h_lens.data(), dc.h_dfs.data(), dc.h_ids.data(),
+			    dc.h_terms.size(), bytes + off[i], off[i + 1] - off[i], k, term_ids + (size_t)i * k,
 			    df + (size_t)i * k, &counts[i], &matches[i]);
 		}
 		px->prof[6] += n;

@@ -55,13 +55,7 @@ struct rt_q_t {
 };
 
 struct rt_state_t {
-	hipStream_t	st;
-	void *		ws;
-	size_t		ws_len;
-	uint8_t *	pin;
-	size_t		pin_len;
-	hipEvent_t	ev[RT_EVENTS];
-	bool		ev_ok;
+	side_t		side;
 	double		prof[NXSGPU_RELATED_PROF];
 };
 
@@ -259,86 +253,11 @@ k_rt_merge(const uint64_t *__restrict__ partial, uint32_t np, uint32_t k, const 
 void
 rt_free(nxsgpu_index_t *ix)
 {
-	rt_state_t *rt = ix->rt;
-
-	if (!rt) {
-		return;
+	if (ix->rt) {
+		side_close(&ix->rt->side, true);
+		delete ix->rt;
+		ix->rt = NULL;
 	}
-	if (rt->st) {
-		(void)hipStreamSynchronize(rt->st);
-		(void)hipStreamDestroy(rt->st);
-	}
-	for (int i = 0; rt->ev_ok && i < RT_EVENTS; i++) {
-		(void)hipEventDestroy(rt->ev[i]);
-	}
-	(void)hipFree(rt->ws);
-	if (rt->pin) {
-		(void)hipHostFree(rt->pin);
-	}
-	delete rt;
-	ix->rt = NULL;
-}
-
-static int
-rt_prepare(nxsgpu_index_t *ix)
-{
-	rt_state_t *rt = ix->rt;
-
-	if (!rt) {
-		rt = new rt_state_t();
-		if (hipStreamCreateWithFlags(&rt->st, hipStreamNonBlocking) != hipSuccess) {
-			delete rt;
-			set_error("related: no stream");
-			return -1;
-		}
-		ix->rt = rt;
-	}
-	if (ix->profiling && !rt->ev_ok) {
-		int made = 0;
-
-		while (made < RT_EVENTS && hipEventCreate(&rt->ev[made]) == hipSuccess) {
-			made++;
-		}
-		if (made < RT_EVENTS) {
-			while (made--) {
-				(void)hipEventDestroy(rt->ev[made]);
-			}
-			set_error("related: no events");
-			return -1;
-		}
-		rt->ev_ok = true;
-	}
-	return 0;
-}
-
-static int
-rt_room(rt_state_t *rt, size_t pin_need, size_t ws_need)
-{
-	if (rt->pin_len < pin_need) {
-		if (rt->pin) {
-			(void)hipHostFree(rt->pin);
-			rt->pin = NULL;
-			rt->pin_len = 0;
-		}
-		if (hipHostMalloc((void **)&rt->pin, pin_need, hipHostMallocDefault) != hipSuccess) {
-			set_error("hipHostMalloc(%zu) for the related staging failed", pin_need);
-			return -1;
-		}
-		rt->pin_len = pin_need;
-	}
-	if (rt->ws_len < ws_need) {
-		if (rt->ws) {
-			(void)hipFree(rt->ws);
-			rt->ws = NULL;
-			rt->ws_len = 0;
-		}
-		if (hipMalloc(&rt->ws, ws_need) != hipSuccess) {
-			set_error("hipMalloc(%zu) for the related workspace failed", ws_need);
-			return -1;
-		}
-		rt->ws_len = ws_need;
-	}
-	return 0;
 }
 
 /* what a pass uploads (q | tok | prog | items | excl) and what it brings back (ids | c | df | counts | matches |
@@ -420,7 +339,7 @@ rt_host(nxsgpu_index_t *ix, const nxsgpu_query_t *plans, const std::vector<uint3
 	std::vector<uint64_t> h_dt(P);
 	std::vector<uint32_t> pres(D), c((size_t)T + 1), df((size_t)T + 1);
 	std::vector<uint8_t> in(D);
-	hipStream_t st = ix->rt->st;
+	hipStream_t st = ix->rt->side.st;
 
 	if ((P && hipMemcpyAsync(h_dt.data(), ix->d_post_dt, P * 8, hipMemcpyDeviceToHost, st) != hipSuccess) ||
 	    hipStreamSynchronize(st) != hipSuccess) {
@@ -566,12 +485,17 @@ nxsgpu_related(nxsgpu_index_t *ix, int algo, const nxsgpu_query_t *plans, uint32
 		set_error("hipSetDevice failed");
 		return -1;
 	}
-	if (rt_prepare(ix) != 0) {
-		return -1;
+	if (!ix->rt) {
+		ix->rt = new rt_state_t();
 	}
 	rt_state_t *rt = ix->rt;
-	hipStream_t st = rt->st;
-	const bool prof = ix->profiling && rt->ev_ok;
+	side_t *sd = &rt->side;
+
+	if (side_open(ix, sd, "related", RT_EVENTS, true) != 0) {
+		return -1;
+	}
+	hipStream_t st = sd->st;
+	const bool prof = ix->profiling && sd->ev_ok;
 	std::vector<uint32_t> u_ids((size_t)nu * k, 0), u_c((size_t)nu * k, 0), u_df((size_t)nu * k, 0), u_counts(nu, 0),
 	    u_matches(nu, 0), u_docs(nu, 0);
 
@@ -600,11 +524,11 @@ nxsgpu_related(nxsgpu_index_t *ix, int algo, const nxsgpu_query_t *plans, uint32
 		const size_t o_part = o_cnt + (((size_t)G * row + 255) & ~(size_t)255);
 		const size_t ws_need = o_part + (size_t)G * np * k * 8 + 512;
 
-		if (rt_room(rt, L0.len + 512, ws_need) != 0) {
+		if (side_room(sd, "related", L0.len + 512, ws_need) != 0) {
 			return -1;
 		}
-		uint8_t *h = (uint8_t *)(((uintptr_t)rt->pin + 255) & ~(uintptr_t)255);
-		uint8_t *d = (uint8_t *)(((uintptr_t)rt->ws + 255) & ~(uintptr_t)255);
+		uint8_t *h = (uint8_t *)(((uintptr_t)sd->pin + 255) & ~(uintptr_t)255);
+		uint8_t *d = (uint8_t *)(((uintptr_t)sd->ws + 255) & ~(uintptr_t)255);
 		uint32_t *d_mask = (uint32_t *)(d + o_mask), *d_cnt = (uint32_t *)(d + o_cnt);
 		uint64_t *d_part = (uint64_t *)(d + o_part);
 
@@ -654,20 +578,20 @@ nxsgpu_related(nxsgpu_index_t *ix, int algo, const nxsgpu_query_t *plans, uint32
 			a.n_docs = D;
 			a.totals = Dv.docs;
 			a.mask = d_mask;
-			if (prof) (void)hipEventRecord(rt->ev[0], st);
+			if (prof) (void)hipEventRecord(sd->ev[0], st);
 			hipLaunchKernelGGL(k_rt_mask, dim3(n_items), dim3(CNT_THREADS), 0, st, a);
-			if (prof) (void)hipEventRecord(rt->ev[1], st);
+			if (prof) (void)hipEventRecord(sd->ev[1], st);
 			if (n_runs) {
 				hipLaunchKernelGGL(k_rt_scan, dim3((uint32_t)n_runs), dim3(RT_THREADS), 0, st, ix->d_post_off, ix->d_post_dt,
 				    (const uint32_t *)d_mask, D, T, p_beg, p_end, run, m, d_cnt);
 			}
-			if (prof) (void)hipEventRecord(rt->ev[2], st);
+			if (prof) (void)hipEventRecord(sd->ev[2], st);
 			hipLaunchKernelGGL(k_rt_select, dim3(np, m), dim3(RT_THREADS), 0, st, ix->d_post_off, (const uint32_t *)d_cnt, T,
 			    (const rt_q_t *)Dv.ex, order, mincount, mindf, np, k, d_part, Dv.matches);
-			if (prof) (void)hipEventRecord(rt->ev[3], st);
+			if (prof) (void)hipEventRecord(sd->ev[3], st);
 			hipLaunchKernelGGL(k_rt_merge, dim3(m), dim3(RT_THREADS), 0, st, (const uint64_t *)d_part, np, k, ix->d_post_off,
 			    (const uint32_t *)d_cnt, T, Dv.ids, Dv.c, Dv.df, Dv.counts);
-			if (prof) (void)hipEventRecord(rt->ev[4], st);
+			if (prof) (void)hipEventRecord(sd->ev[4], st);
 			if (hipGetLastError() != hipSuccess) {
 				set_error("related kernel launch failed");
 				(void)hipStreamSynchronize(st);
@@ -686,10 +610,7 @@ nxsgpu_related(nxsgpu_index_t *ix, int algo, const nxsgpu_query_t *plans, uint32
 			memcpy(u_docs.data() + u0, H.docs, (size_t)m * 4);
 			if (prof) {
 				for (int e = 0; e < 4; e++) {
-					float ms = 0;
-
-					(void)hipEventElapsedTime(&ms, rt->ev[e], rt->ev[e + 1]);
-					rt->prof[3 + e] += ms;
+					rt->prof[3 + e] += side_elapsed(sd, e, e + 1);
 				}
 			}
 			rt->prof[0] += m;

@@ -31,9 +31,9 @@
  * (The layout -- parts per pattern, 256-entry tiles, a top-k per workgroup instead of per wavefront -- was
  * chosen from counts, not from a measurement: NOTES.md.)
  *
- * The pass runs on the order's stream (px_state_t::st: a completion and a wildcard pass are both blocking,
- * one after the other) with a grow-only workspace, pinned staging and events of its own: beside batches and
- * fuzzy passes in flight, none of their slots.  Under NXS_GPU_WILDCARD=host every pattern takes the host
+ * The pass runs on the order's stream (the prefix state's side_t::st: a completion and a wildcard pass are both
+ * blocking, one after the other) with a grow-only workspace, pinned staging and events of its own (a side_t that
+ * borrows that stream): beside batches and fuzzy passes in flight, none of their slots.  Under NXS_GPU_WILDCARD=host every pattern takes the host
  * ranker (nxs_wild_rank) over a host copy of the BK image: the cross-check route.
  */
 #include "nxs_gpu_int.h"
@@ -51,12 +51,7 @@ struct wc_pat_t {
 };
 
 struct wc_state_t {
-	void *		ws;
-	size_t		ws_len;
-	uint8_t *	pin;
-	size_t		pin_len;
-	hipEvent_t	ev[4];
-	bool		ev_ok;
+	side_t		side;		/* (st is the prefix state's: wc_prepare) */
 	double		prof[NXSGPU_WILDCARD_PROF];
 };
 
@@ -179,16 +174,7 @@ wc_free(nxsgpu_index_t *ix)
 	if (!wc) {
 		return;
 	}
-	if (ix->px && ix->px->st) {
-		(void)hipStreamSynchronize(ix->px->st);
-	}
-	for (int i = 0; wc->ev_ok && i < 4; i++) {
-		(void)hipEventDestroy(wc->ev[i]);
-	}
-	(void)hipFree(wc->ws);
-	if (wc->pin) {
-		(void)hipHostFree(wc->pin);
-	}
+	side_close(&wc->side, false);	/* (waits for the prefix state's stream: px_free destroys it, afterwards) */
 	delete wc;
 	ix->wc = NULL;
 }
@@ -196,24 +182,14 @@ wc_free(nxsgpu_index_t *ix)
 static int
 wc_prepare(nxsgpu_index_t *ix)
 {
-	wc_state_t *wc = ix->wc;
-
-	if (!wc) {
-		wc = new wc_state_t();
-		ix->wc = wc;
+	if (!ix->wc) {
+		ix->wc = new wc_state_t();
 	}
-	if (ix->profiling && !wc->ev_ok) {
-		bool ok = true;
-		for (int i = 0; i < 4 && ok; i++) {
-			ok = hipEventCreate(&wc->ev[i]) == hipSuccess;
-		}
-		if (!ok) {
-			set_error("wildcard: no events");
-			return -1;
-		}
-		wc->ev_ok = true;
+	if (side_open(ix, &ix->wc->side, "wildcard", 4, false) != 0 || px_prepare(ix, ix->cfg.wild_host) != 0) {
+		return -1;
 	}
-	return px_prepare(ix, ix->cfg.wild_host);
+	ix->wc->side.st = ix->px->side.st;
+	return 0;
 }
 
 /* one device pass over n patterns (a chunk): one upload from pinned memory, the kernels, one copy back; blocking */
@@ -223,53 +199,31 @@ wc_pass(nxsgpu_index_t *ix, const uint8_t *bytes, const uint32_t *off, uint32_t 
 {
 	px_state_t *px = ix->px;
 	wc_state_t *wc = ix->wc;
+	side_t *sd = &wc->side;
 	const uint32_t cap = ix->cfg.wild_parts;
 	const uint32_t blen = off[n] - off[0];
-	const size_t rows = (size_t)n * k;
-	/* up: pattern records | head offsets | pattern bytes | head bytes; down: term ids | df | counts | matches */
+	/* up: pattern records | head offsets | pattern bytes | head bytes; down: the term-list block */
 	const size_t o_hoff = (size_t)n * sizeof(wc_pat_t), o_pb = o_hoff + ((size_t)n + 1) * 4;
 	const size_t o_hb = (o_pb + blen + 15) & ~(size_t)15;
 	const size_t up_bytes = (o_hb + blen + 16 + 15) & ~(size_t)15;
-	const size_t dn_bytes = ((rows * 2 + (size_t)n * 2) * 4 + 15) & ~(size_t)15;
-	const size_t pin_need = up_bytes + dn_bytes;
-	const size_t need = up_bytes + dn_bytes + (size_t)n * sizeof(uint2) + (size_t)n * cap * k * 8 + 4 * 256;
-	hipStream_t st = px->st;
-	const bool prof = ix->profiling && wc->ev_ok;
+	const size_t dn_bytes = tl_bytes(n, k);
+	hipStream_t st = sd->st;
+	const bool prof = ix->profiling && sd->ev_ok;
 
-	if (wc->pin_len < pin_need) {
-		if (wc->pin) {
-			(void)hipHostFree(wc->pin);
-			wc->pin = NULL;
-			wc->pin_len = 0;
-		}
-		if (hipHostMalloc((void **)&wc->pin, pin_need + pin_need / 2, hipHostMallocDefault) != hipSuccess) {
-			set_error("hipHostMalloc(%zu) for the wildcard staging failed", pin_need);
-			return -1;
-		}
-		wc->pin_len = pin_need + pin_need / 2;
+	if (side_room(sd, "wildcard", up_bytes + dn_bytes,
+	    up_bytes + dn_bytes + (size_t)n * sizeof(uint2) + (size_t)n * cap * k * 8 + 4 * 256) != 0) {
+		return -1;
 	}
-	if (wc->ws_len < need) {
-		if (wc->ws) {
-			(void)hipFree(wc->ws);
-			wc->ws = NULL;
-			wc->ws_len = 0;
-		}
-		if (hipMalloc(&wc->ws, need) != hipSuccess) {
-			set_error("hipMalloc(%zu) for the wildcard workspace failed", need);
-			return -1;
-		}
-		wc->ws_len = need;
-	}
-	wc_pat_t *const h_pat = (wc_pat_t *)wc->pin;
-	uint32_t *const h_hoff = (uint32_t *)(wc->pin + o_hoff);
-	uint8_t *const h_pb = wc->pin + o_pb, *const h_hb = wc->pin + o_hb;
-	uint8_t *const h_dn = wc->pin + up_bytes;
-	uint8_t *p = (uint8_t *)wc->ws;
+	wc_pat_t *const h_pat = (wc_pat_t *)sd->pin;
+	uint32_t *const h_hoff = (uint32_t *)(sd->pin + o_hoff);
+	uint8_t *const h_pb = sd->pin + o_pb, *const h_hb = sd->pin + o_hb;
+	uint8_t *const h_dn = sd->pin + up_bytes;
+	uint8_t *p = (uint8_t *)sd->ws;
 	uint8_t *d_up = carve<uint8_t>(p, up_bytes);
 	uint8_t *d_dn = carve<uint8_t>(p, dn_bytes);
 	uint2 *d_range = carve<uint2>(p, n);
 	uint64_t *d_partial = carve<uint64_t>(p, (size_t)n * cap * k);
-	uint32_t *d_ids = (uint32_t *)d_dn, *d_df = d_ids + rows, *d_counts = d_df + rows, *d_matches = d_counts + n;
+	const tl_block_t d = tl_layout(d_dn, n, k);
 	uint32_t hlen = 0;
 
 	memcpy(h_pb, bytes + off[0], blen);
@@ -286,19 +240,19 @@ wc_pass(nxsgpu_index_t *ix, const uint8_t *bytes, const uint32_t *off, uint32_t 
 		hlen += head;
 	}
 	h_hoff[n] = hlen;
-	if (hipMemcpyAsync(d_up, wc->pin, up_bytes, hipMemcpyHostToDevice, st) != hipSuccess ||
+	if (hipMemcpyAsync(d_up, sd->pin, up_bytes, hipMemcpyHostToDevice, st) != hipSuccess ||
 	    hipMemsetAsync(d_dn, 0, dn_bytes, st) != hipSuccess) {
 		set_error("wildcard upload failed");
 		return -1;
 	}
-	if (prof) (void)hipEventRecord(wc->ev[0], st);
+	if (prof) (void)hipEventRecord(sd->ev[0], st);
 	px_launch_range(ix, st, d_up + o_hb, (const uint32_t *)(d_up + o_hoff), n, d_range, NULL);
-	if (prof) (void)hipEventRecord(wc->ev[1], st);
+	if (prof) (void)hipEventRecord(sd->ev[1], st);
 	hipLaunchKernelGGL(k_wc_match, dim3(cap, n), dim3(WC_GROUP), 0, st, ix->d_bk, ix->d_bk_bytes, px->d_node, px->d_key,
-	    d_range, (const wc_pat_t *)d_up, d_up + o_pb, cap, k, d_partial, d_matches);
-	if (prof) (void)hipEventRecord(wc->ev[2], st);
-	hipLaunchKernelGGL(k_wc_merge, dim3(n), dim3(WC_GROUP), 0, st, d_partial, d_range, cap, k, d_ids, d_df, d_counts);
-	if (prof) (void)hipEventRecord(wc->ev[3], st);
+	    d_range, (const wc_pat_t *)d_up, d_up + o_pb, cap, k, d_partial, d.matches);
+	if (prof) (void)hipEventRecord(sd->ev[2], st);
+	hipLaunchKernelGGL(k_wc_merge, dim3(n), dim3(WC_GROUP), 0, st, d_partial, d_range, cap, k, d.ids, d.df, d.counts);
+	if (prof) (void)hipEventRecord(sd->ev[3], st);
 	if (hipGetLastError() != hipSuccess) {
 		set_error("wildcard kernel launch failed");
 		(void)hipStreamSynchronize(st);
@@ -309,24 +263,15 @@ wc_pass(nxsgpu_index_t *ix, const uint8_t *bytes, const uint32_t *off, uint32_t 
 		set_error("wildcard pass failed: %s", hipGetErrorString(hipGetLastError()));
 		return -1;
 	}
-	const uint32_t *h_ids = (const uint32_t *)h_dn, *h_df = h_ids + rows, *h_counts = h_df + rows, *h_matches = h_counts + n;
 	wc->prof[0] += 1;
 	wc->prof[8] += n;
 	if (prof) {
-		float ms = 0;
-		(void)hipEventElapsedTime(&ms, wc->ev[0], wc->ev[3]);
-		wc->prof[1] += ms;
-		(void)hipEventElapsedTime(&ms, wc->ev[0], wc->ev[1]);
-		wc->prof[2] += ms;
-		(void)hipEventElapsedTime(&ms, wc->ev[1], wc->ev[2]);
-		wc->prof[3] += ms;
-		(void)hipEventElapsedTime(&ms, wc->ev[2], wc->ev[3]);
-		wc->prof[4] += ms;
+		wc->prof[1] += side_elapsed(sd, 0, 3);
+		for (int e = 0; e < 3; e++) {
+			wc->prof[2 + e] += side_elapsed(sd, e, e + 1);
+		}
 	}
-	memcpy(o_ids, h_ids, rows * 4);
-	memcpy(o_df, h_df, rows * 4);
-	memcpy(o_counts, h_counts, (size_t)n * 4);
-	memcpy(o_matches, h_matches, (size_t)n * 4);
+	tl_copy_out(h_dn, n, k, o_ids, o_df, o_counts, o_matches);
 	return 0;
 }
 
@@ -334,16 +279,10 @@ extern "C" int
 nxsgpu_wildcard(nxsgpu_index_t *ix, const uint8_t *bytes, const uint32_t *off, uint32_t n, uint32_t k,
     uint32_t *term_ids, uint32_t *df, uint32_t *counts, uint32_t *matches)
 {
-	if (k < 1 || k > NXS_WILD_MAX) {
-		set_error("nxsgpu_wildcard: k is 1..%d", NXS_WILD_MAX);
-		return -1;
-	}
-	if (n == 0) {
-		return 0;
-	}
-	if (n > (1u << 24) || off[n] - off[0] > (1u << 30)) {
-		set_error("nxsgpu_wildcard: too many patterns");
-		return -1;
+	const int go = tl_enter(ix, "nxsgpu_wildcard", "patterns", k, NXS_WILD_MAX, off, n, term_ids, df, counts, matches);
+
+	if (go != 0) {
+		return go < 0 ? -1 : 0;
 	}
 	for (uint32_t i = 0; i < n; i++) {
 		if (off[i + 1] < off[i] || off[i + 1] - off[i] > NXS_WILD_MAXLEN) {
@@ -351,24 +290,18 @@ nxsgpu_wildcard(nxsgpu_index_t *ix, const uint8_t *bytes, const uint32_t *off, u
 			return -1;
 		}
 	}
-	if (hipSetDevice(ix->device) != hipSuccess) {
-		set_error("hipSetDevice failed");
-		return -1;
-	}
 	if (wc_prepare(ix) != 0) {
 		return -1;
 	}
 	px_state_t *px = ix->px;
 	wc_state_t *wc = ix->wc;
 
-	memset(term_ids, 0, (size_t)n * k * 4);
-	memset(df, 0, (size_t)n * k * 4);
-	memset(counts, 0, (size_t)n * 4);
-	memset(matches, 0, (size_t)n * 4);
 	if (ix->cfg.wild_host) {
+		const dict_host_t &dc = px->dict;
+
 		for (uint32_t i = 0; i < n; i++) {
-			nxs_wild_rank(px->h_terms.data(), px->h_lens.data(), px->h_dfs.data(), px->h_ids.data(),
-			    px->h_terms.size(), bytes + off[i], off[i + 1] - off[i], k, term_ids + (size_t)i * k,
+			nxs_wild_rank(dc.h_terms.data(), dc.h_lens.data(), dc.h_dfs.data(), dc.h_ids.data(),
+			    dc.h_terms.size(), bytes + off[i], off[i + 1] - off[i], k, term_ids + (size_t)i * k,
 			    df + (size_t)i * k, &counts[i], &matches[i]);
 		}
 		wc->prof[6] += n;
@@ -403,7 +336,7 @@ nxsgpu_wildcard_profile(nxsgpu_index_t *ix, double out[NXSGPU_WILDCARD_PROF], in
 		}
 	}
 	if (ix->px) {
-		out[5] = ix->cfg.wild_host ? (double)ix->px->h_terms.size() : (double)ix->px->n_e;
+		out[5] = ix->cfg.wild_host ? (double)ix->px->dict.h_terms.size() : (double)ix->px->n_e;
 		out[7] = (double)ix->px->builds;
 	}
 }

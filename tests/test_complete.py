@@ -173,13 +173,14 @@ def test_sort_chunk_boundaries(nxs, tmp_path, monkeypatch, route):
 
 # ---- 4. selection sizes --------------------------------------------------------------------
 
-SIZES = (0, 1, 63, 64, 65, 257)
+SIZES = (0, 1, 63, 64, 65, 255, 256, 257, 513)
 
 
 @ROUTES
 def test_selection_sizes(nxs, tmp_path, monkeypatch, route):
-    """Ranges of 0, 1, 63, 64, 65 and 257 eligible terms: with equal df (`e<n>_`: the term id decides) and with
-    df strictly increasing with the term id (`i<n>_`: the last entries win)."""
+    """Ranges of 0, 1, 63, 64, 65, 255, 256, 257 and 513 eligible terms (255 / 256: where a thread's first entry
+    ends and its stride begins in the 256-thread selection; 513: threads stride twice): with equal df (`e<n>_`:
+    the term id decides) and with df strictly increasing with the term id (`i<n>_`: the last entries win)."""
     term_dfs = []
     for n in SIZES:
         term_dfs += [(b"e%d_%03d" % (n, j), 3) for j in range(n)]
@@ -191,10 +192,11 @@ def test_selection_sizes(nxs, tmp_path, monkeypatch, route):
         prefixes = [b"e%d_" % n for n in SIZES] + [b"i%d_" % n for n in SIZES] + [b"e", b"i", b"e6", b"i25"]
         for k in KS:
             got = check(gidx, truth, prefixes, k, route)
-            assert [g.matches for g in got[:12]] == list(SIZES) * 2
-            for n, g in zip(SIZES, got[:6]):
+            ns = len(SIZES)
+            assert [g.matches for g in got[:2 * ns]] == list(SIZES) * 2
+            for n, g in zip(SIZES, got[:ns]):
                 assert [t for t, _, _ in g] == [b"e%d_%03d" % (n, j) for j in range(min(k, n))]
-            for n, g in zip(SIZES, got[6:12]):
+            for n, g in zip(SIZES, got[ns:2 * ns]):
                 assert [df for _, _, df in g] == list(range(n, n - min(k, n), -1))
     finally:
         set_route(monkeypatch, gidx, None)
