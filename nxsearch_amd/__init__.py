@@ -101,6 +101,7 @@ NXS_H_SYMBOLS = [
 # csrc/nxs_hooks.h: test hooks + bench accessors, only in builds with -DNXS_TEST_HOOKS (the default)
 NXS_HOOK_SYMBOLS = ["nxs_index_device", "nxs_index_host_profile", "nxs_index_shard_info", "nxs_test_pool", "nxs_test_assemble",
                     "nxs_test_index_image", "nxsgpu_test_index_image",
+                    "nxs_test_term_image", "nxsgpu_test_term_image",
                     "nxs_test_fixup_scan", "nxs_test_inject_failure", "nxs_test_count_tile_widths",
                     "nxs_test_suggest_host", "nxs_test_suggest_params", "nxs_test_sugg_build",
                     "nxs_test_complete_host", "nxs_test_complete_params", "nxs_test_compl_build",
@@ -149,6 +150,17 @@ IMG_PARTS = {"doc_ids": (1, "<u8"), "doc_len": (2, "<u4"), "post_off": (3, "<u8"
              "outl_max": (13, "<u4"), "bm_terms": (14, "<u4"), "blkmap": (15, "<u8"), "bmrank": (16, "<u4")}
 IMG_DF_GLOBAL = 17      # u32[T + 2], a doc shard's collection-wide df (N4); no bytes on a whole index
 IMG_PER_ALGO = (5, 7, 9)
+# nxs_test_term_image: the same for the term-side state, as nxsgpu_test_term_image (csrc/nxs_gpu_fuzzy.hip) has them
+TIMG_SCALARS = 0
+TIMG_SCALAR_NAMES = ["n_bk", "bk_depth", "bk_bytes_len", "n_fz", "sg_gen", "sg_built", "sg_built_gen", "sg_n_c",
+                     "px_gen", "px_built", "px_built_gen", "px_n_e", "px_builds"]
+TIMG_PARTS = {"bk": (1, "bk"), "bk_bytes": (2, "u1"), "bk_parent": (3, "<u4"), "bk_slot": (4, "u1"),
+              "fz_node": (5, "<u4"), "fz_sig": (6, "<u4"), "fz_len": (7, "u1"), "fz_len_start": (8, "<u4"),
+              "sg_node": (9, "<u4"), "sg_sig": (10, "<u4"), "sg_len": (11, "u1"),
+              "px_node": (12, "<u4"), "px_key": (13, "<u8")}
+# nxsgpu_bknode_t (include/nxs_gpu.h) as a numpy record
+TIMG_BK_DTYPE = [("bitmap", "<u8"), ("first_child", "<u4"), ("term_id", "<u4"), ("str_off", "<u4"),
+                 ("str_len", "<u2"), ("flags", "<u2"), ("inl", "u1", (8,))]
 
 _lib = None
 
@@ -1001,6 +1013,36 @@ class Index:
             out["dense_q8"] = out["dense_q8"].reshape(-1, sc["dense_q8_stride"])
         dfg = part(IMG_DF_GLOBAL, np.dtype("<u4"))
         out["df_global"] = dfg if dfg.size else None
+        return out
+
+    def term_image(self):
+        """nxs_test_term_image(): the term-side device state read back as numpy arrays, for the test that compares
+        it with a host model: {"scalars": {...}, "bk": the nodes (records of nxsgpu_bknode_t), "bk_bytes",
+        "bk_parent", "bk_slot", "fz_node", "fz_sig", "fz_len", "fz_len_start", "sg_node", "sg_sig", "sg_len",
+        "px_node", "px_key"}.  Nothing is built by the call: a part that is not materialised is an empty array, and
+        the scalars say which generation suggest's candidates and the completion order were built for.  Not while
+        batches are in flight."""
+        import numpy as np
+        L = lib()
+        L.nxs_test_term_image.restype = C.c_int
+        L.nxs_test_term_image.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+
+        def part(no, dtype):
+            need = C.c_size_t()
+            if L.nxs_test_term_image(self._h, no, None, 0, C.byref(need)) != 0:
+                self.nxs._raise()
+            buf = np.empty(need.value, dtype=np.uint8)
+            if need.value:
+                got = C.c_size_t()
+                if L.nxs_test_term_image(self._h, no, buf.ctypes.data, buf.nbytes, C.byref(got)) != 0:
+                    self.nxs._raise()
+                assert got.value == need.value, (no, got.value, need.value)
+            return buf.view(dtype)
+
+        raw = part(TIMG_SCALARS, np.uint64)
+        out = {"scalars": {name: int(raw[i]) for i, name in enumerate(TIMG_SCALAR_NAMES)}}
+        for name, (no, dtype) in TIMG_PARTS.items():
+            out[name] = part(no, np.dtype(TIMG_BK_DTYPE if dtype == "bk" else dtype))
         return out
 
     def reconfigure(self):

@@ -1755,3 +1755,136 @@ nxsgpu_suggest_profile(nxsgpu_index_t *ix, double out[NXSGPU_SUGGEST_PROF], int 
 		}
 	}
 }
+
+#ifdef NXS_TEST_HOOKS
+/*
+ * The device half of nxs_test_term_image (nxs_hooks.h): one part of the term-side state, read back for the test
+ * that compares it with a host model (tests/test_term_image.py) -- the BK image, the side arrays and candidates of
+ * the match-first search, suggest's candidates, and (through px_test_image) the order that completion and wildcard
+ * matching read.  The rules are nxsgpu_test_index_image's: *need = the part's bytes (0: not materialised), copied
+ * to `out` if cap holds them; the index's streams and the two states' streams are waited for, device arrays come
+ * back by plain hipMemcpy, and NOTHING is built: a state whose generation is behind comes back as it is, which is
+ * what the scalars are for.  The part numbers and the scalars' order are restated in nxsearch_amd/__init__.py
+ * (TIMG_*).
+ */
+extern "C" int
+nxsgpu_test_term_image(nxsgpu_index_t *ix, int part, void *out, size_t cap, size_t *need)
+{
+	enum { P_SCALARS, P_BK, P_BK_BYTES, P_BK_PARENT, P_BK_SLOT, P_FZ_NODE, P_FZ_SIG, P_FZ_LEN, P_FZ_LEN_START,
+	    P_SG_NODE, P_SG_SIG, P_SG_LEN, P_PX_NODE, P_PX_KEY, P_COUNT };
+	const sg_state_t *sg = ix->sg;
+	const uint32_t *px_node = NULL;
+	const uint64_t *px_key = NULL;
+	const void *src = NULL;		/* host memory, or (dev) device memory */
+	bool dev = true;
+	size_t len = 0;
+	uint64_t sc[16] = { 0 }, pxs[4];
+
+	*need = 0;
+	if (part < 0 || part >= P_COUNT) {
+		set_error("nxsgpu_test_term_image: no part %d", part);
+		return -1;
+	}
+	if (test_image_enter(ix, "nxsgpu_test_term_image") != 0) {
+		return -1;
+	}
+	if (sg && sg->side.st && hipStreamSynchronize(sg->side.st) != hipSuccess) {
+		set_error("nxsgpu_test_term_image: hipStreamSynchronize failed");
+		return -1;
+	}
+	if (px_test_image(ix, pxs, &px_node, &px_key) != 0) {
+		return -1;
+	}
+	/* (the side arrays exist with the image or not at all: bk_aux_build) */
+	const bool aux = ix->n_bk && ix->d_bk_parent;
+	const size_t n_fz = aux ? ix->n_fz : 0, n_sg = sg && sg->built ? sg->n_c : 0, n_px = pxs[0] ? pxs[2] : 0;
+
+	switch (part) {
+	case P_SCALARS:
+		sc[0] = ix->n_bk;
+		sc[1] = ix->bk_depth;
+		sc[2] = ix->bk_bytes_len;
+		sc[3] = ix->n_fz;
+		sc[4] = ix->sg_gen;
+		sc[5] = sg ? sg->built : 0;
+		sc[6] = sg ? sg->built_gen : 0;
+		sc[7] = sg ? sg->n_c : 0;
+		sc[8] = ix->px_gen;
+		sc[9] = pxs[0];
+		sc[10] = pxs[1];
+		sc[11] = pxs[2];
+		sc[12] = pxs[3];
+		src = sc;
+		len = sizeof(sc);
+		dev = false;
+		break;
+	case P_BK:
+		src = ix->d_bk;
+		len = (size_t)ix->n_bk * sizeof(nxsgpu_bknode_t);
+		break;
+	case P_BK_BYTES:
+		src = ix->d_bk_bytes;
+		len = ix->n_bk ? ix->bk_bytes_len : 0;
+		break;
+	case P_BK_PARENT:
+		src = ix->d_bk_parent;
+		len = aux ? (size_t)ix->n_bk * 4 : 0;
+		break;
+	case P_BK_SLOT:
+		src = ix->d_bk_slot;
+		len = aux ? (size_t)ix->n_bk : 0;
+		break;
+	case P_FZ_NODE:
+		src = ix->d_fz_node;
+		len = n_fz * 4;
+		break;
+	case P_FZ_SIG:
+		src = ix->d_fz_sig;
+		len = n_fz * 4;
+		break;
+	case P_FZ_LEN:
+		src = ix->d_fz_len;
+		len = n_fz;
+		break;
+	case P_FZ_LEN_START:
+		src = ix->fz_len_start.data();
+		len = aux ? ix->fz_len_start.size() * 4 : 0;
+		dev = false;
+		break;
+	case P_SG_NODE:
+		src = sg ? sg->d_node : NULL;
+		len = n_sg * 4;
+		break;
+	case P_SG_SIG:
+		src = sg ? sg->d_sig : NULL;
+		len = n_sg * 4;
+		break;
+	case P_SG_LEN:
+		src = sg ? sg->d_len : NULL;
+		len = n_sg;
+		break;
+	case P_PX_NODE:
+		src = px_node;
+		len = n_px * 4;
+		break;
+	case P_PX_KEY:
+		src = px_key;
+		len = n_px * 8;
+		break;
+	}
+	if (!src) {
+		len = 0;
+	}
+	*need = len;
+	if (!len || !out || cap < len) {
+		return 0;
+	}
+	if (!dev) {
+		memcpy(out, src, len);
+	} else if (hipMemcpy(out, src, len, hipMemcpyDeviceToHost) != hipSuccess) {
+		set_error("nxsgpu_test_term_image: hipMemcpy of part %d failed", part);
+		return -1;
+	}
+	return 0;
+}
+#endif /* NXS_TEST_HOOKS */

@@ -1305,6 +1305,7 @@ nxsgpu_index_create(int device, const nxsgpu_index_src_t *src)
 	ix->first_bad = ~0ull;
 	ix->n_bk = src->n_bk;
 	ix->bk_depth = src->bk_depth;
+	ix->bk_bytes_len = src->n_bk ? src->bk_bytes_len : 0;
 	memset(&ix->prof, 0, sizeof(ix->prof));
 
 	if (D >= (1ull << 32) || P >= (1ull << 40)) {
@@ -1826,6 +1827,7 @@ nxsgpu_index_set_bk(nxsgpu_index_t *ix, const nxsgpu_bknode_t *nodes, uint32_t n
 	ix->d_bk_bytes = NULL;
 	ix->n_bk = 0;
 	ix->bk_depth = 0;
+	ix->bk_bytes_len = 0;
 	if (n == 0) {
 		return 0;
 	}
@@ -1841,6 +1843,7 @@ nxsgpu_index_set_bk(nxsgpu_index_t *ix, const nxsgpu_bknode_t *nodes, uint32_t n
 	}
 	ix->n_bk = n;
 	ix->bk_depth = depth;
+	ix->bk_bytes_len = bytes_len;
 	return 0;
 }
 
@@ -1920,6 +1923,28 @@ nxsgpu_index_set_global_df(nxsgpu_index_t *ix, const uint32_t *df, uint32_t n_te
 extern "C" uint64_t nxsgpu_index_impact_passes(const nxsgpu_index_t *ix) { return ix->n_impact_passes; }
 
 #ifdef NXS_TEST_HOOKS
+int
+test_image_enter(nxsgpu_index_t *ix, const char *fn)
+{
+	if (nxsgpu_batches_in_flight(ix)) {
+		set_error("%s: batches are in flight", fn);
+		return -1;
+	}
+	if (hipSetDevice(ix->device) != hipSuccess) {
+		set_error("hipSetDevice failed");
+		return -1;
+	}
+	const hipStream_t sts[] = { ix->stream, ix->stream2, ix->stream3, ix->stream_up, ix->stream_down, ix->stream_fz,
+	    ix->stream_rp[1], ix->xstream[0], ix->xstream[1], ix->xstream[2], ix->stream_cnt };
+	for (hipStream_t st : sts) {
+		if (st && hipStreamSynchronize(st) != hipSuccess) {
+			set_error("%s: hipStreamSynchronize failed", fn);
+			return -1;
+		}
+	}
+	return 0;
+}
+
 /*
  * The device half of nxs_test_index_image (nxs_hooks.h): one part of the index image, read back for
  * the tests that compare it with a host model (tests/test_index_image.py, tests/test_docshard_image.py).  *need = the part's bytes
@@ -1947,23 +1972,8 @@ nxsgpu_test_index_image(nxsgpu_index_t *ix, int part, int algo, void *out, size_
 		set_error("nxsgpu_test_index_image: no part %d of ranking function %d", part, algo);
 		return -1;
 	}
-	if (nxsgpu_batches_in_flight(ix)) {
-		set_error("nxsgpu_test_index_image: batches are in flight");
+	if (test_image_enter(ix, "nxsgpu_test_index_image") != 0) {
 		return -1;
-	}
-	if (hipSetDevice(ix->device) != hipSuccess) {
-		set_error("hipSetDevice failed");
-		return -1;
-	}
-	{
-		const hipStream_t sts[] = { ix->stream, ix->stream2, ix->stream3, ix->stream_up, ix->stream_down, ix->stream_fz,
-		    ix->stream_rp[1], ix->xstream[0], ix->xstream[1], ix->xstream[2], ix->stream_cnt };
-		for (hipStream_t st : sts) {
-			if (st && hipStreamSynchronize(st) != hipSuccess) {
-				set_error("nxsgpu_test_index_image: hipStreamSynchronize failed");
-				return -1;
-			}
-		}
 	}
 	switch (part) {
 	case P_SCALARS:

@@ -364,6 +364,7 @@ struct nxsgpu_index {
 	nxsgpu_bknode_t *d_bk;
 	uint8_t *	d_bk_bytes;
 	uint32_t	n_bk, bk_depth;
+	uint64_t	bk_bytes_len;	/* of d_bk_bytes (16 spare bytes follow) */
 	/* match-first fuzzy search (k_fz_filter ...): per node the byte-set signature
 	 * and length of its term, its parent and the slot it hangs in (k_bk_aux) */
 	bool		fz_split;	/* nxsgpu_fuzzy is working on one half of a batch it split */
@@ -655,6 +656,11 @@ int	rebuild_impacts(nxsgpu_index_t *ix, unsigned only = 3);	/* bit a: ranking fu
 int	ensure_algo(nxsgpu_index_t *ix, int algo);
 void	warm_streams(nxsgpu_index_t *ix);
 void	pick_record_stream(nxsgpu_index_t *ix);
+#ifdef NXS_TEST_HOOKS
+/* how the read-back hooks (nxs_hooks.h) begin: refused while batches are in flight, the device set, every stream
+ * of the index waited for.  0 / -1 ("<fn>: ...") */
+int	test_image_enter(nxsgpu_index_t *ix, const char *fn);
+#endif
 
 /* ---- nxs_gpu_fuzzy.hip ---- */
 void	bk_aux_free(nxsgpu_index_t *ix);
@@ -755,6 +761,11 @@ int	px_prepare(nxsgpu_index_t *ix, bool host);
 void	px_launch_range(nxsgpu_index_t *ix, hipStream_t st, const uint8_t *d_bytes, const uint32_t *d_off, uint32_t n,
 	    uint2 *d_range, uint32_t *d_matches);
 void	px_free(nxsgpu_index_t *ix);		/* everything nxsgpu_complete has built (index destroy) */
+#ifdef NXS_TEST_HOOKS
+/* nxsgpu_test_term_image's view of the order (nxs_hooks.h): waits for the state's stream; sc = built, built_gen,
+ * n_e, builds (zeros while there is no state); the arrays as they are (NULL: none).  Builds nothing.  0 / -1 */
+int	px_test_image(nxsgpu_index_t *ix, uint64_t sc[4], const uint32_t **d_node, const uint64_t **d_key);
+#endif
 
 /* ---- nxs_gpu_wild.hip ---- */
 void	wc_free(nxsgpu_index_t *ix);		/* everything nxsgpu_wildcard has built (index destroy, before px_free) */

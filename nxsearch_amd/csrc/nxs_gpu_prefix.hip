@@ -234,6 +234,32 @@ px_free(nxsgpu_index_t *ix)
 	ix->px = NULL;
 }
 
+#ifdef NXS_TEST_HOOKS
+int
+px_test_image(nxsgpu_index_t *ix, uint64_t sc[4], const uint32_t **d_node, const uint64_t **d_key)
+{
+	const px_state_t *px = ix->px;
+
+	memset(sc, 0, 4 * sizeof(uint64_t));
+	*d_node = NULL;
+	*d_key = NULL;
+	if (!px) {
+		return 0;
+	}
+	if (px->side.st && hipStreamSynchronize(px->side.st) != hipSuccess) {
+		set_error("nxsgpu_test_term_image: hipStreamSynchronize failed");
+		return -1;
+	}
+	sc[0] = px->built;
+	sc[1] = px->built_gen;
+	sc[2] = px->n_e;
+	sc[3] = px->builds;
+	*d_node = px->d_node;
+	*d_key = px->d_key;
+	return 0;
+}
+#endif /* NXS_TEST_HOOKS */
+
 /* the order of the index's current generation, on the device */
 static int
 px_build_order(nxsgpu_index_t *ix)

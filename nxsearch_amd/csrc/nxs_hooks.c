@@ -319,6 +319,24 @@ nxs_test_index_image(nxs_index_t *idx, int part, int algo, void *out, size_t cap
 	return 0;
 }
 
+/* ... and of the term-side state (nxs_hooks.h): read in nxs_gpu_fuzzy.hip and nxs_gpu_prefix.hip */
+int
+nxs_test_term_image(nxs_index_t *idx, int part, void *out, size_t cap, size_t *need)
+{
+	struct nxsgpu_index *dev = nxs_index_device(idx);
+
+	*need = 0;
+	if (!dev) {
+		nxs_decl_err(idx->nxs, NXS_ERR_INVALID, "the index has no device image");
+		return -1;
+	}
+	if (nxsgpu_test_term_image(dev, part, out, cap, need) != 0) {
+		nxs_decl_err(idx->nxs, NXS_ERR_SYSTEM, "%s", nxsgpu_last_error());
+		return -1;
+	}
+	return 0;
+}
+
 /* nxs_ex_ordinal for every q[i] over ids[0 .. n) (UINT64_MAX: not a live doc) */
 void
 nxs_test_explain_ordinal(const uint64_t *ids, uint64_t n, const uint64_t *q, size_t nq, uint64_t *out)

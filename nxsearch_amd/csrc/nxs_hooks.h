@@ -37,6 +37,16 @@ struct nxsgpu_index *nxs_index_device(nxs_index_t *);
 int		nxs_test_index_image(nxs_index_t *, int part, int algo, void *out, size_t cap, size_t *need);
 /* ... its device half (nxs_gpu_index.hip); the error is nxsgpu_last_error() */
 int		nxsgpu_test_index_image(struct nxsgpu_index *, int part, int algo, void *out, size_t cap, size_t *need);
+/*
+ * One part of the term-side device state, read back under the same rules: the BK image (nodes, byte pool), the
+ * side arrays of the match-first fuzzy search (parent, slot) and its candidates (node, signature, length, the first
+ * candidate of every length), suggest's candidates, and the byte order of the live terms with its selection keys
+ * that completion and wildcard matching read (the parts and the scalars' order: nxsgpu_test_term_image in
+ * nxs_gpu_fuzzy.hip, which reaches the order through nxs_gpu_prefix.hip; TIMG_* in nxsearch_amd/__init__.py).
+ * Builds nothing: a lazily built state that is behind its generation comes back as it is, and says so in the scalars.
+ */
+int		nxs_test_term_image(nxs_index_t *, int part, void *out, size_t cap, size_t *need);
+int		nxsgpu_test_term_image(struct nxsgpu_index *, int part, void *out, size_t cap, size_t *need);
 /* the plan cache (query string -> compiled plan) on / off at run time */
 void		nxs_index_set_plan_cache(nxs_index_t *, int on);
 

@@ -183,6 +183,9 @@ struct nxs_index {
 	struct nxs_bktree *bktree;
 	uint32_t	bk_upto;
 	bool		bk_flags_stale;
+	/* the "total > 0" flag of every node of the image the device holds, BFS order (bk_flags_keep) */
+	uint8_t *	bk_flags;
+	uint32_t	bk_flags_n;
 	uint64_t	n_incremental, n_rebuilds;
 };
 

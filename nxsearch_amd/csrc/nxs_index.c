@@ -450,6 +450,37 @@ nxs_bk_free(nxs_bkimage_t *bk)
 	memset(bk, 0, sizeof(*bk));
 }
 
+/* remember the flags of the image that has just gone to the device (out of memory: none are remembered, and
+ * the next nxs_index_bk_sync uploads whatever it flattens) */
+static void
+bk_flags_keep(nxs_index_t *idx, const nxs_bkimage_t *bk)
+{
+	free(idx->bk_flags);
+	idx->bk_flags_n = 0;
+	idx->bk_flags = bk->n ? malloc(bk->n) : NULL;
+	if (idx->bk_flags) {
+		for (uint32_t i = 0; i < bk->n; i++) {
+			idx->bk_flags[i] = (uint8_t)bk->nodes[i].flags;
+		}
+		idx->bk_flags_n = bk->n;
+	}
+}
+
+/* does the device hold exactly these flags?  (Only asked when no term was added: the numbering is the same.) */
+static bool
+bk_flags_same(const nxs_index_t *idx, const nxs_bkimage_t *bk)
+{
+	if (idx->bk_flags_n != bk->n) {
+		return false;
+	}
+	for (uint32_t i = 0; i < bk->n; i++) {
+		if (idx->bk_flags[i] != (uint8_t)bk->nodes[i].flags) {
+			return false;
+		}
+	}
+	return true;
+}
+
 /* ---- doc blocks ---------------------------------------------------------- */
 
 typedef struct {
@@ -793,6 +824,7 @@ nxs_index_load(nxs_index_t *idx, const char *terms_path, const char *dtmap_path)
 			idx->hdr_docs_seen = src.hdr_doc_count;
 			idx->hdr_tokens_seen = src.hdr_token_count;
 			idx->bk_flags_stale = false;
+			bk_flags_keep(idx, &bk);
 			ret = 0;
 			break;
 		}
@@ -823,6 +855,9 @@ unload_snapshot(nxs_index_t *idx)
 	free(idx->terms);
 	free(idx->thash);
 	nxs_bktree_destroy(idx->bktree);
+	free(idx->bk_flags);
+	idx->bk_flags = NULL;
+	idx->bk_flags_n = 0;
 	free(idx->h_doc_ids);
 	free(idx->h_blk_off);
 	free(idx->h_npairs);
@@ -926,6 +961,8 @@ rebuild_snapshot(nxs_index_t *idx)
 	idx->bktree = tmp.bktree;
 	idx->bk_upto = tmp.bk_upto;
 	idx->bk_flags_stale = false;
+	idx->bk_flags = tmp.bk_flags;
+	idx->bk_flags_n = tmp.bk_flags_n;
 	idx->h_doc_ids = tmp.h_doc_ids;
 	idx->h_blk_off = tmp.h_blk_off;
 	idx->h_npairs = tmp.h_npairs;
@@ -1434,12 +1471,21 @@ nxs_index_bk_sync(nxs_index_t *idx)
 		nxs_decl_err(idx->nxs, NXS_ERR_SYSTEM, "out of memory");
 		goto out;
 	}
+	/* only totals moved and every flag is what the device holds: the image, the side arrays built from it and
+	 * the generations of suggest's candidates and the completion order stay */
+	if (idx->bk_upto == idx->last_id && bk_flags_same(idx, &bk)) {
+		idx->bk_flags_stale = false;
+		ret = 0;
+		goto out;
+	}
 	if (nxsgpu_index_set_bk(idx->dev, bk.nodes, bk.n, bk.depth, bk.bytes, bk.bytes_len) != 0) {
 		nxs_decl_err(idx->nxs, NXS_ERR_SYSTEM, "%s", nxsgpu_last_error());
+		idx->bk_flags_n = 0;	/* (the device may hold no image now: whatever comes next is uploaded) */
 		goto out;
 	}
 	idx->bk_upto = idx->last_id;
 	idx->bk_flags_stale = false;
+	bk_flags_keep(idx, &bk);
 	ret = 0;
 out:
 	nxs_bk_free(&bk);
