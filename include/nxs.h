@@ -390,6 +390,51 @@ int		nxs_index_related_batch(nxs_index_t *, nxs_params_t *, const char *const *q
 bool		nxs_sugg_docs(const nxs_sugg_t *, uint64_t *docs);
 
 /*
+ * ---- search within a doc-id set (new) -------------------------------------------------
+ *
+ * nxs_index_search_docs ranks a caller's candidates: the docs of an access-control list, of an earlier result
+ * list, of another index.  Raising "limit" and filtering afterwards is not the same thing: the reference's
+ * comparator calls equal scores equal (result_entry_cmp), so which of several tied docs survive a capped heap
+ * depends on the feed sequence, and taking docs out of that sequence changes the outcome.
+ *
+ * PARSING AND PARAMETERS.  Query i is parsed, filtered and resolved exactly as nxs_index_search would with the same
+ * params: "limit", "algo", "fuzzymatch", "prefixmatch" / "prefix_limit", "wildcardmatch" / "wildcard_terms",
+ * "total" and "explain" are read as a search reads them.
+ *
+ * THE SET.  Let R be the results of that query at an unbounded limit, as (doc, score) pairs; the scores are the
+ * index's: N, df, adl and idf do not depend on the set.  Let S be the distinct ids of docs[i] that are live docs
+ * of the snapshot.  Duplicates count once.  Ids never seen or removed are ignored silently: a stale
+ * access-control list is normal, not an error.
+ *
+ * THE RESPONSE is exactly what the reference produces when nxs_resp_addresult is reached only for docs of S: R n S
+ * is fed in descending doc id (results.c prepends, the build walks the list) into the reference's capped heap of
+ * "limit" entries, then heap_sort runs; ties fall where that heap puts them.  A doc of S is in R when the
+ * expression holds on its presence mask and at least one present token has a non-negative float
+ * (search.c:251-258).  With "total": nxs_resp_total = |R n S|.  With "explain": as a search's.  An empty S,
+ * n_docs[i] == 0 with docs[i] == NULL, or a query that resolves to nothing all give an empty response with
+ * total 0.
+ *
+ * ERRORS.  n_docs[i] > NXS_DOCSET_MAX: NXS_ERR_LIMIT "doc set too large".  More than 32 live tokens (a search's
+ * wide plan): NXS_ERR_LIMIT "search_docs is not available for a query of more than 32 terms".  A parse error is
+ * what a search reports.  In a batch all three are errs[i], and the batch goes on.  On a handle from
+ * nxs_index_open_shard: NXS_ERR_INVALID "search_docs is not available on a doc shard".
+ *
+ * SHARED SETS.  Two queries of a batch whose docs[i] pointer and n_docs[i] are both equal share one set: it is
+ * sorted and resolved once (one access-control list across many queries).
+ *
+ * Everything else is nxs_index_related's: the call re-syncs with the files as a search does, is allowed with
+ * batches or a pending fuzzy pass in flight and neither reorders them nor changes their responses, runs on a
+ * stream and workspace of its own and is blocking, and is local under a communicator: no collective, and "total"
+ * is served.  nxs_index_search_docs_batch returns the number of failed queries, or -1 if the batch as a whole
+ * could not run.
+ */
+#define	NXS_DOCSET_MAX		(1u << 22)
+nxs_resp_t *	nxs_index_search_docs(nxs_index_t *, nxs_params_t *, const char *query, size_t len,
+		    const nxs_doc_id_t *docs, size_t n_docs);
+int		nxs_index_search_docs_batch(nxs_index_t *, nxs_params_t *, const char *const *queries, size_t n,
+		    const nxs_doc_id_t *const *docs, const size_t *n_docs, nxs_resp_t **resps, nxs_err_t *errs);
+
+/*
  * Batch entry point (new).  Runs `n` queries with one set of params as one
  * device batch.  resps[i] receives a response object or NULL if query i
  * failed (its code/message are then in errs[i]/the nxs_t error slot for the

@@ -496,6 +496,48 @@ int		nxsgpu_related(nxsgpu_index_t *, int algo, const nxsgpu_query_t *plans, uin
 void		nxsgpu_related_profile(nxsgpu_index_t *, double out[NXSGPU_RELATED_PROF], int reset);
 
 /*
+ * ---- search within a doc-id set ---------------------------------------------------------
+ *
+ * nxsgpu_search_docs: for each of n plans the results of the plan restricted to its set -- sets[set_of[i]], set_len
+ * ids, ASCENDING AND DISTINCT (csrc/nxs_docset.h: nxs_ds_sort_unique), at most NXSGPU_DOCSET_MAX; an id that is not
+ * in the doc table is ignored, a removed doc keeps its ordinal and matches nothing.  A doc of the set is a result
+ * when the plan's expression holds on its presence mask and at least one present token has a non-negative float;
+ * its score is the f32 sum of those floats in ascending token order (the REGULAR posting of a TF-IDF dense term,
+ * as nxsgpu_explain reads it).  The results are fed in descending doc id into the reference's capped heap of
+ * `limit` (>= 1, any value) entries and sorted by its heap_sort (k_replay): res as nxsgpu_search fills it;
+ * totals[n] (may be NULL) = the results before the cap.  The impacts of `algo` are materialised on demand.  0 / -1.
+ *
+ * A plan of more than 8 tokens is evaluated from its postfix program on a 64-bit stack: a program that names a token
+ * >= n_tokens, underflows, leaves nothing or is deeper than 64 fails the call (nxs_ds_prog_ok; what the host's
+ * compiler emits never is).
+ *
+ * The scoring is driven from the docs (|set| x tokens lookups; no list is streamed).  k_ds_ord resolves the ids of
+ * the call's distinct sets to ordinals ONCE, before the passes: the ids go up in slices, the ordinals stay on the host
+ * (4 B an id).  k_ds_score -- a wavefront per (query, chunk of NXS_GPU_DOCSET_CHUNK, default 1024, a multiple of 64,
+ * entries), a lane per doc, the token loop wave-uniform -- compacts the matches of a chunk into its candidate segment in
+ * descending doc order, and the replay takes the segments from the last to the first: the heap across the lanes up to
+ * limit 64, in LDS up to 8000, in global memory with capacity min(limit, |set|) beyond.  A pass serves whole queries,
+ * one at least, within NXS_GPU_DOCSET_WS (default NXSGPU_DOCSET_WS) bytes of workspace, and uploads the ordinals of
+ * the sets its queries use.  The call has a stream, a grow-only workspace, pinned staging and events of its own:
+ * allowed while batches and fuzzy passes are in flight, takes none of their slots; blocking.  An index that is never
+ * asked allocates, uploads and launches nothing.  Under NXS_GPU_DOCSET=host (the cross-check route) the index arrays
+ * are copied back, the ordinals and every (query, doc) are evaluated on the host by the same nxs_ds_lane, and the
+ * candidates go through the same device replay.
+ *
+ * nxsgpu_search_docs_profile: since the last reset -- out[0] calls that reached the device, out[1] passes, out[2]
+ * distinct sets resolved, out[3] ids resolved, out[4] / out[5] (query, doc) cells scored on the device / on the
+ * host, out[6] candidates, out[7] / out[8] / out[9] HIP-event ms of k_ds_ord / k_ds_score / k_replay (with
+ * nxsgpu_set_profiling only).
+ */
+#define	NXSGPU_DOCSET_MAX	(1u << 22)
+#define	NXSGPU_DOCSET_PROF	12
+#define	NXSGPU_DOCSET_WS	(256ull << 20)
+int		nxsgpu_search_docs(nxsgpu_index_t *, int algo, uint64_t limit, const nxsgpu_query_t *plans, uint32_t n,
+		    const uint64_t *const *sets, const uint32_t *set_len, uint32_t n_sets, const uint32_t *set_of,
+		    nxsgpu_results_t *res, uint32_t *totals);
+void		nxsgpu_search_docs_profile(nxsgpu_index_t *, double out[NXSGPU_DOCSET_PROF], int reset);
+
+/*
  * ---- host batches as fixed-size records; query sharding over several GPUs ----
  *
  * The reference scales out by running independent worker processes

@@ -97,6 +97,7 @@ NXS_H_SYMBOLS = [
     "nxs_index_doc_terms", "nxs_index_doc_terms_batch", "nxs_sugg_score",
     "nxs_index_similar", "nxs_index_similar_batch",
     "nxs_index_related", "nxs_index_related_batch", "nxs_sugg_docs",
+    "nxs_index_search_docs", "nxs_index_search_docs_batch",
 ]
 # csrc/nxs_hooks.h: test hooks + bench accessors, only in builds with -DNXS_TEST_HOOKS (the default)
 NXS_HOOK_SYMBOLS = ["nxs_index_device", "nxs_index_host_profile", "nxs_index_shard_info", "nxs_test_pool", "nxs_test_assemble",
@@ -113,7 +114,8 @@ NXS_HOOK_SYMBOLS = ["nxs_index_device", "nxs_index_host_profile", "nxs_index_sha
                     "nxs_test_docterms_params", "nxs_test_docterms_build", "nxs_test_docterms_lane",
                     "nxs_test_docterms_key", "nxs_test_similar_drop",
                     "nxs_test_related_params", "nxs_test_related_build", "nxs_test_related_key",
-                    "nxs_test_related_share", "nxs_test_related_eligible", "nxs_test_related_rank"]
+                    "nxs_test_related_share", "nxs_test_related_eligible", "nxs_test_related_rank",
+                    "nxs_test_docset_sort", "nxs_test_docset_lane"]
 NXS_GPU_H_SYMBOLS = [
     "nxsgpu_device_count", "nxsgpu_last_error", "nxsgpu_index_create",
     "nxsgpu_index_destroy", "nxsgpu_index_df", "nxsgpu_index_postings",
@@ -137,6 +139,7 @@ NXS_GPU_H_SYMBOLS = [
     "nxsgpu_explain", "nxsgpu_explain_profile",
     "nxsgpu_doc_terms", "nxsgpu_doc_terms_profile",
     "nxsgpu_related", "nxsgpu_related_profile",
+    "nxsgpu_search_docs", "nxsgpu_search_docs_profile",
 ]
 
 # nxs_test_index_image (csrc/nxs_hooks.h): part numbers and the order of the scalars, as nxsgpu_test_index_image
@@ -375,6 +378,24 @@ def lib():
         L.nxs_test_related_rank.restype = C.c_int
         L.nxs_test_related_rank.argtypes = [C.c_int, u32p, u32p, C.c_uint32, C.c_uint32, C.c_uint32, u32p, C.c_uint32,
                                             C.c_uint32, u32p, C.POINTER(C.c_uint64)]
+    u64p = C.POINTER(C.c_uint64)
+    L.nxs_index_search_docs.restype = vp
+    L.nxs_index_search_docs.argtypes = [vp, vp, C.c_char_p, C.c_size_t, u64p, C.c_size_t]
+    L.nxs_index_search_docs_batch.restype = C.c_int
+    L.nxs_index_search_docs_batch.argtypes = [vp, vp, C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(u64p),
+                                              C.POINTER(C.c_size_t), C.POINTER(vp), C.POINTER(C.c_int)]
+    L.nxsgpu_search_docs.restype = C.c_int
+    L.nxsgpu_search_docs.argtypes = [vp, C.c_int, C.c_uint64, C.POINTER(GpuQuery), C.c_uint32, C.POINTER(u64p), u32p,
+                                     C.c_uint32, u32p, C.POINTER(GpuResults), u32p]
+    L.nxsgpu_search_docs_profile.restype = None
+    L.nxsgpu_search_docs_profile.argtypes = [vp, C.POINTER(C.c_double), C.c_int]
+    if hasattr(L, "nxs_test_docset_sort"):
+        L.nxs_test_docset_sort.restype = C.c_size_t
+        L.nxs_test_docset_sort.argtypes = [u64p, C.c_size_t]
+        L.nxs_test_docset_lane.restype = C.c_int
+        L.nxs_test_docset_lane.argtypes = [u64p, C.POINTER(C.c_float), u64p, C.c_uint32, C.c_bool, C.c_uint32, u32p,
+                                           C.POINTER(C.c_uint8), C.c_uint32, u32p, C.c_size_t, C.POINTER(C.c_uint8),
+                                           C.POINTER(C.c_float)]
     L.nxsgpu_wildcard_profile.restype = None
     L.nxsgpu_wildcard_profile.argtypes = [vp, C.POINTER(C.c_double), C.c_int]
     L.nxsgpu_explain_profile.restype = None
@@ -1299,6 +1320,66 @@ class Index:
         lib().nxsgpu_related_profile(self.device, out, 1 if reset else 0)
         return {"device_queries": int(out[0]), "host_queries": int(out[1]), "passes": int(out[2]), "mask_ms": out[3],
                 "scan_ms": out[4], "select_ms": out[5], "merge_ms": out[6], "calls": int(out[7])}
+
+    def search_docs(self, queries, docs, limit=None, algo=None, fuzzymatch=None, total=False, prefixmatch=None,
+                    prefix_limit=None, explain=False, wildcardmatch=None, wildcard_terms=None, json=False):
+        """nxs_index_search_docs_batch(): every query ranked within a set of doc ids -> result lists as search_batch
+        returns them (an NxsError instance in the slot of a query that failed: a parse error, more than 32 terms, a
+        set of more than 2^22 ids).  `docs`: one sequence of ids (a list, or a numpy uint64 array) shared by all
+        queries, or a sequence with one such sequence (or None: the empty set) per query -- entries that are the
+        same object share one set, which is then sorted and resolved once.  Duplicates count once, ids that are not
+        live docs are ignored.  json: the responses' JSON texts."""
+        L = lib()
+        n = len(queries)
+        per_query = len(docs) > 0 and (docs[0] is None or hasattr(docs[0], "__len__"))
+        if per_query and len(docs) != n:
+            raise ValueError("search_docs: one doc set per query, or one set for all")
+        u64p = C.POINTER(C.c_uint64)
+        made = {}
+
+        def c_set(d):
+            if d is None or len(d) == 0:
+                return (None, u64p(), 0)
+            if id(d) not in made:
+                if hasattr(d, "ctypes"):
+                    import numpy as np
+                    a = np.ascontiguousarray(d, dtype=np.uint64)
+                    made[id(d)] = (a, a.ctypes.data_as(u64p), len(a))
+                else:
+                    a = (C.c_uint64 * len(d))(*d)
+                    made[id(d)] = (a, C.cast(a, u64p), len(d))
+            return made[id(d)]
+        sets = [c_set(docs[i] if per_query else docs) for i in range(n)]
+        ptrs = (u64p * max(n, 1))(*[x[1] for x in sets])
+        lens = (C.c_size_t * max(n, 1))(*[x[2] for x in sets])
+        qs = (C.c_char_p * max(n, 1))(*[_b(q) for q in queries])
+        resps = (C.c_void_p * max(n, 1))()
+        errs = (C.c_int * max(n, 1))()
+        p = _make_params(limit, algo, fuzzymatch, total, prefixmatch, prefix_limit, explain, wildcardmatch, wildcard_terms)
+        try:
+            r = L.nxs_index_search_docs_batch(self._h, p, qs, n, ptrs, lens, resps, errs)
+        finally:
+            if p:
+                L.nxs_params_release(p)
+        if r < 0:
+            self.nxs._raise()
+        out = []
+        for i in range(n):
+            if resps[i]:
+                out.append(_take(L.nxs_resp_tojson(resps[i], None)) if json else _drain(resps[i], explain))
+                L.nxs_resp_release(resps[i])
+            else:
+                out.append(NxsError(errs[i], "query %d failed" % i))
+        return out
+
+    def search_docs_profile(self, reset=False):
+        """nxsgpu_search_docs_profile(): calls that reached the device, passes, distinct sets and ids resolved,
+        (query, doc) cells scored on the device / on the host, candidates, HIP-event ms per kernel (profiling on)."""
+        out = (C.c_double * 12)()
+        lib().nxsgpu_search_docs_profile(self.device, out, 1 if reset else 0)
+        return {"calls": int(out[0]), "passes": int(out[1]), "sets": int(out[2]), "ids": int(out[3]),
+                "device_cells": int(out[4]), "host_cells": int(out[5]), "candidates": int(out[6]), "ord_ms": out[7],
+                "score_ms": out[8], "replay_ms": out[9]}
 
     def explain_profile(self, reset=False):
         """nxsgpu_explain_profile(): explain passes, HIP-event ms of k_explain (profiling on), (result, token)

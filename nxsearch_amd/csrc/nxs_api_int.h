@@ -8,6 +8,7 @@
  *   nxs_plan.c      plan cache and the front half of a batch (parse, lookups, prefixes, misses, compile)
  *   nxs_batch.c     begin / end, the late second half, exact fix-up and its protocol, query sharding
  *   nxs_lookup.c    nxs_sugg_t, suggest, complete, wildcard, doc_terms, related
+ *   nxs_searchdocs.c  search within a caller's doc-id set (search_docs)
  *   nxs_docshard.c  doc-sharded collections: search, attach, refresh
  *   nxs_hooks.c     the test hooks that reach no static
  *
@@ -210,6 +211,10 @@ int	late_finish(nxs_index_t *);
 void	index_drain(nxs_index_t *);
 
 /* ---- nxs_lookup.c ---------------------------------------------------------------------- */
+
+/* how every blocking side call begins (`what` names it in the refusal on a doc shard; bk: it reads the BK image):
+ * refusals, the batch bound, the re-sync with the files.  0 / -1 with the error declared */
+int	lookup_enter(nxs_index_t *, const char *what, size_t n, bool bk);
 
 /* the rows nxsgpu_doc_terms fills for n docs at k terms each */
 typedef struct {

@@ -149,6 +149,12 @@ cfg_from_env(gpu_cfg_t &c)
 	c.related_run = (uint32_t)u64("NXS_GPU_RELATED_RUN", 4096, 64, 1u << 20);
 	c.related_parts = (uint32_t)u64("NXS_GPU_RELATED_PARTS", 64, 1, 1024);
 	c.related_ws = u64("NXS_GPU_RELATED_WS", NXSGPU_RELATED_WS, 1, 1ull << 34);
+	{
+		const char *e = getenv("NXS_GPU_DOCSET");
+		c.docset_host = e && !strcmp(e, "host");
+	}
+	c.docset_chunk = std::max<uint32_t>(WAVE, (uint32_t)u64("NXS_GPU_DOCSET_CHUNK", 1024, 64, 1u << 16) / WAVE * WAVE);
+	c.docset_ws = u64("NXS_GPU_DOCSET_WS", NXSGPU_DOCSET_WS, 1, 1ull << 34);
 }
 
 /* ------------------------------------------------------------------ */
@@ -681,6 +687,7 @@ nxsgpu_index_destroy(nxsgpu_index_t *ix)
 	ex_free(ix);
 	dv_free(ix);
 	rt_free(ix);
+	ds_free(ix);
 	bk_aux_free(ix);
 	(void)hipFree(ix->ws);
 	(void)hipFree(ix->fz);

@@ -39,7 +39,10 @@
  *  nxs_gpu_related.hip    related terms of a query's matches: the doc sets of a group of plans as bits (k_rt_mask: k_count_tile's
  *                         body), one pass over the posting array that meets every list with them (k_rt_scan), a top-k
  *                         per plan and part (k_rt_select), the parts merged (k_rt_merge); nxs_related.h
- *  nxs_gpu_side.hip       host only: what the six blocking side passes above share -- stream, workspace, staging and
+ *  nxs_gpu_docset.hip     a search within a caller's doc-id set: the sets' ordinals (k_ds_ord), every (query, doc of its set)
+ *                         scored by lookups from the doc's side (k_ds_score; nxs_docset.h) into candidate segments, then
+ *                         k_replay
+ *  nxs_gpu_side.hip       host only: what the seven blocking side passes above share -- stream, workspace, staging and
  *                         events (side_t), the host rankers' dictionary, the term-list download block
  *  nxs_gpu_plan.hip       host only: query classes, the work list (build_worklist) and
  *                         the layout of a batch's arrays (batch_layout)
@@ -209,6 +212,12 @@ struct gpu_cfg_t {
 					 * workgroup each (k_rt_select) */
 	uint64_t	related_ws;	/* NXS_GPU_RELATED_WS (256 MiB): bytes of count rows per pass; the group is what fits (one plan
 					 * at least, 32 at most), a larger batch is cut into passes */
+	bool		docset_host;	/* NXS_GPU_DOCSET=host: ordinals and nxs_ds_lane (nxs_docset.h) on the host over copies of the
+					 * index arrays, the candidates through the same device replay: the cross-check */
+	uint32_t	docset_chunk;	/* NXS_GPU_DOCSET_CHUNK (1024): entries of a set per wavefront of k_ds_score and slots of its
+					 * candidate segment; a multiple of 64, 64 at least */
+	uint64_t	docset_ws;	/* NXS_GPU_DOCSET_WS (256 MiB): bytes of workspace per pass; a larger batch is cut into passes
+					 * of whole queries (one at least) */
 };
 enum : uint32_t { COUNT_AUTO = 0, COUNT_TILE = 1, COUNT_REQ = 2, COUNT_SCAN = 3 };
 
@@ -437,6 +446,8 @@ struct nxsgpu_index {
 	struct dv_state_t *dv;
 	/* related terms (nxsgpu_related, nxs_gpu_related.hip): the same; nothing until the first call */
 	struct rt_state_t *rt;
+	/* search within a doc-id set (nxsgpu_search_docs, nxs_gpu_docset.hip): the same; nothing until the first call */
+	struct ds_state_t *ds;
 };
 
 static inline uint32_t __device__ __host__
@@ -670,7 +681,7 @@ void	sg_free(nxsgpu_index_t *ix);		/* everything nxsgpu_suggest has built (index
 
 /* ---- nxs_gpu_side.hip ---- */
 /*
- * What every blocking side pass (suggest, complete, wildcard, explain, doc terms, related) owns beside its own
+ * What every blocking side pass (suggest, complete, wildcard, explain, doc terms, related, search_docs) owns beside its own
  * data: a non-blocking stream, a grow-only device workspace, grow-only pinned staging and, once profiling is on,
  * its events.  Zero-initialised with the pass's state; nothing exists until side_open / side_room make it.
  */
@@ -778,6 +789,9 @@ void	dv_free(nxsgpu_index_t *ix);		/* everything nxsgpu_doc_terms has built (ind
 
 /* ---- nxs_gpu_related.hip ---- */
 void	rt_free(nxsgpu_index_t *ix);		/* everything nxsgpu_related has built (index destroy) */
+
+/* ---- nxs_gpu_docset.hip ---- */
+void	ds_free(nxsgpu_index_t *ix);		/* everything nxsgpu_search_docs has built (index destroy) */
 
 /* ---- nxs_gpu_plan.hip ---- */
 void	delete_worklist(worklist_t *);

@@ -34,7 +34,7 @@
  * never reach the device: docs 0, no term.  The pass has a stream, grow-only workspace, pinned staging and
  * events of its own: beside batches and fuzzy passes in flight, none of their slots; blocking.  Nothing exists
  * until the first call.  Under NXS_GPU_RELATED=host the posting array is copied back, the doc set is evaluated
- * from the plan's postfix program, the counts are taken by a plain loop over the lists and ranked by
+ * from the plan's postfix program (nxs_ds_eval, nxs_docset.h), the counts are taken by a plain loop over the lists and ranked by
  * nxs_rt_rank: the cross-check route.
  */
 #include <string>
@@ -43,6 +43,7 @@
 #include "nxs_gpu_int.h"
 #include "nxs_gpu_dev.h"
 #include "nxs_related.h"
+#include "nxs_docset.h"
 
 #define	RT_THREADS	256
 #define	RT_GROUP_MAX	32u		/* plans per pass at most: the bits of a mask word */
@@ -297,29 +298,6 @@ rt_layout(uint8_t *base, uint32_t G, uint64_t items, uint32_t k)
 	return L;
 }
 
-/* the postfix program on a presence mask, on the host (the kernels' eval_prog is device code) */
-static bool
-rt_eval_host(const uint8_t *prog, uint32_t len, uint32_t m)
-{
-	bool st[NXSGPU_MAX_PROG + 1];
-	uint32_t sp = 0;
-
-	for (uint32_t i = 0; i < len; i++) {
-		const uint8_t op = prog[i];
-
-		if (op < NXSGPU_MAX_TOKENS) {
-			st[sp++] = (m >> op) & 1u;
-		} else if (op == NXSGPU_OP_EMPTY) {
-			st[sp++] = false;
-		} else if (sp >= 2) {
-			const bool b = st[--sp], a = st[--sp];
-
-			st[sp++] = op == NXSGPU_OP_AND ? (a && b) : op == NXSGPU_OP_OR ? (a || b) : (a && !b);
-		}
-	}
-	return sp ? st[sp - 1] : false;
-}
-
 /* the posting range of a plan's token (beyond the snapshot's terms: no postings yet, like count_prepare) */
 static inline void
 rt_tok_range(const nxsgpu_index_t *ix, uint32_t tid, uint64_t *pb, uint64_t *pe)
@@ -367,7 +345,7 @@ rt_host(nxsgpu_index_t *ix, const nxsgpu_query_t *plans, const std::vector<uint3
 			}
 		}
 		for (uint64_t d = 0; d < D; d++) {
-			in[d] = pres[d] != 0 && rt_eval_host(q.prog, q.prog_len, pres[d]);
+			in[d] = pres[d] != 0 && nxs_ds_eval(q.prog, q.prog_len, pres[d]);
 			n += in[d];
 		}
 		std::fill(c.begin(), c.end(), 0u);
@@ -447,6 +425,11 @@ nxsgpu_related(nxsgpu_index_t *ix, int algo, const nxsgpu_query_t *plans, uint32
 		}
 		if (!valid || q.n_tokens == 0 || D == 0 || T == 0) {
 			continue;
+		}
+		/* (the program is evaluated above 8 tokens, and for every plan on the host route) */
+		if ((q.n_tokens > 8 || ix->cfg.related_host) && !nxs_ds_prog_ok(q.prog, q.prog_len, q.n_tokens)) {
+			set_error("query %u: a malformed postfix program, or one deeper than 64", i);
+			return -1;
 		}
 		for (uint32_t j = 0; j < q.n_tokens; j++) {
 			uint64_t pb, pe;

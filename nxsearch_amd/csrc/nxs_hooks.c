@@ -16,6 +16,7 @@
 #include "nxs_explain.h"
 #include "nxs_docterms.h"
 #include "nxs_related.h"
+#include "nxs_docset.h"
 
 char *
 nxs_test_query_repr(const char *query, char **errmsg)
@@ -296,6 +297,73 @@ nxs_test_related_rank(int order, const uint32_t *c, const uint32_t *df, uint32_t
     uint32_t mindf, const uint32_t *excl, uint32_t n_excl, uint32_t k, uint32_t *out_ids, uint64_t *matches)
 {
 	return nxs_rt_rank(order, c, df, n_terms, mincount, mindf, excl, n_excl, k, out_ids, matches);
+}
+
+/* nxs_docset.h: the set as the device wants it, and one lane of k_ds_score over arrays handed in */
+size_t
+nxs_test_docset_sort(uint64_t *ids, size_t n)
+{
+	return nxs_ds_sort_unique(ids, n);
+}
+
+/*
+ * nxs_ds_lane over arrays handed in: nt lists back to back in dt / imp (list j = positions off[j] .. off[j + 1],
+ * dt entries doc << 32 | tf, ascending by doc, docs below n_docs), the plan's truth table and program, and nd doc
+ * ordinals.  bitmap: every list through a block-presence bitmap and rank directory built here as the device
+ * index builds its rows.  hit[i] / score[i]: the lane's answer for ords[i].  0 / -1 (out of memory, nt > 32).
+ */
+int
+nxs_test_docset_lane(const uint64_t *dt, const float *imp, const uint64_t *off, uint32_t nt, bool bitmap, uint32_t n_docs,
+    const uint32_t *truth, const uint8_t *prog, uint32_t prog_len, const uint32_t *ords, size_t nd, uint8_t *hit,
+    float *score)
+{
+	const uint64_t words = ((uint64_t)n_docs + 4095) / 4096, P = (nt && nt <= NXSGPU_MAX_TOKENS) ? off[nt] : 0;
+	nxs_ds_tok_t toks[NXSGPU_MAX_TOKENS];
+	nxs_ds_post_t *post = NULL;
+	uint64_t *bm = NULL;
+	uint32_t *rk = NULL;
+	int ret = -1;
+
+	if (nt > NXSGPU_MAX_TOKENS) {
+		return -1;
+	}
+	post = calloc(P ? P : 1, sizeof(*post));
+	bm = calloc((size_t)nt * (words ? words : 1) + 1, sizeof(uint64_t));
+	rk = calloc((size_t)nt * (words + 1) + 1, sizeof(uint32_t));
+	if (!post || !bm || !rk) {
+		goto out;
+	}
+	for (uint64_t p = 0; p < P; p++) {
+		post[p].doc = (uint32_t)(dt[p] >> 32);
+		post[p].imp = imp[p];
+	}
+	for (uint32_t j = 0; j < nt; j++) {
+		toks[j].beg = off[j];
+		toks[j].end = off[j + 1];
+		toks[j].row = bitmap ? j : NXS_DS_NONE;
+		toks[j].pad = 0;
+		for (uint64_t w = 0, i = off[j]; bitmap && w <= words; w++) {
+			while (i < off[j + 1] && ((dt[i] >> 32) >> 12) < w) {
+				i++;
+			}
+			rk[(size_t)j * (words + 1) + w] = (uint32_t)(i - off[j]);
+		}
+		for (uint64_t i = off[j]; bitmap && i < off[j + 1]; i++) {
+			const uint32_t d = (uint32_t)(dt[i] >> 32);
+
+			bm[(size_t)j * words + (d >> 12)] |= UINT64_C(1) << ((d >> 6) & 63);
+		}
+	}
+	for (size_t i = 0; i < nd; i++) {
+		score[i] = 0.0f;
+		hit[i] = ords[i] < n_docs && nxs_ds_lane(ords[i], nt, toks, truth, prog, prog_len, dt, post, bm, rk, words, &score[i]);
+	}
+	ret = 0;
+out:
+	free(post);
+	free(bm);
+	free(rk);
+	return ret;
 }
 
 /*

@@ -186,5 +186,15 @@ int		nxs_test_related_rank(int order, const uint32_t *c, const uint32_t *df, uin
 		    uint32_t mindf, const uint32_t *excl, uint32_t n_excl, uint32_t k, uint32_t *out_ids,
 		    uint64_t *matches);
 
+/* search within a doc-id set: nxs_ds_sort_unique on ids[0 .. n) in place (-> how many are left), and nxs_ds_lane
+ * (nxs_docset.h) over arrays handed in, in the style of nxs_test_docterms_lane: nt lists back to back in dt / imp
+ * (list j = positions off[j] .. off[j + 1]; dt entries doc << 32 | tf, ascending by doc, docs below n_docs; imp
+ * the float of the same position), the plan's truth table and postfix program, nd doc ordinals; bitmap: every list
+ * through a block bitmap + rank directory built from it.  hit[i] / score[i]: the lane's answer for ords[i].  0 / -1 */
+size_t		nxs_test_docset_sort(uint64_t *ids, size_t n);
+int		nxs_test_docset_lane(const uint64_t *dt, const float *imp, const uint64_t *off, uint32_t nt, bool bitmap,
+		    uint32_t n_docs, const uint32_t *truth, const uint8_t *prog, uint32_t prog_len, const uint32_t *ords,
+		    size_t nd, uint8_t *hit, float *score);
+
 #endif /* NXS_TEST_HOOKS */
 #endif /* NXS_HOOKS_H */

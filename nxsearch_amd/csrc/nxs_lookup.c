@@ -225,7 +225,7 @@ lookup_free(lookup_t *st)
 
 /* what comes before the strings are looked at, and after the caller has read its params (bk: the call reads
  * the BK image).  0 / -1 */
-static int
+int
 lookup_enter(nxs_index_t *idx, const char *what, size_t n, bool bk)
 {
 	nxs_t *nxs = idx->nxs;
