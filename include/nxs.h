@@ -50,7 +50,8 @@ nxs_err_t	nxs_get_error(const nxs_t *, const char **);	/* nxs.h:48 */
  * prefix_limit / explain / wildcardmatch / wildcard_terms, nxs_index_suggest reads suggest_limit /
  * suggest_maxdist, nxs_index_complete complete_limit, nxs_index_wildcard wildcard_limit, nxs_index_doc_terms
  * docterms_limit / docterms_mindf, nxs_index_similar similar_terms / similar_mindf / similar_self,
- * nxs_index_related related_limit / related_order / related_mindf / related_mincount / related_self */
+ * nxs_index_related related_limit / related_order / related_mindf / related_mincount / related_self,
+ * nxs_index_match_docs match_limit / match_from */
 struct nxs_params;
 typedef struct nxs_params nxs_params_t;
 
@@ -433,6 +434,62 @@ nxs_resp_t *	nxs_index_search_docs(nxs_index_t *, nxs_params_t *, const char *qu
 		    const nxs_doc_id_t *docs, size_t n_docs);
 int		nxs_index_search_docs_batch(nxs_index_t *, nxs_params_t *, const char *const *queries, size_t n,
 		    const nxs_doc_id_t *const *docs, const size_t *n_docs, nxs_resp_t **resps, nxs_err_t *errs);
+
+/*
+ * ---- a query's matches listed by doc id (new) -----------------------------------------
+ *
+ * nxs_index_match_docs returns the doc set of a query itself, not a ranked and capped view of it: for export,
+ * delete-by-query or re-index-by-query in the system that owns the documents, joins against another store, a stable
+ * scroll through all hits, "search within these results".  Raising "limit" does none of this: a capped heap is
+ * tie-order dependent and a deep page of it has no stable cursor.
+ *
+ * DOC SET.  M is the doc set of the query's expression: exactly what "total" counts and what nxs_index_related
+ * calls M -- live docs only, and empty under a ranking function that scores nothing.  The query is parsed, filtered
+ * and resolved as nxs_index_search would with the same params: "algo", "fuzzymatch", "prefixmatch" /
+ * "prefix_limit", "wildcardmatch" / "wildcard_terms" are read as a search reads them; "limit", "total" and
+ * "explain" are ignored.
+ *
+ * KEYS.  "match_limit" (uint, 1..NXS_MATCH_MAX, default 1000): the size of a page.  "match_from" (uint, default 0):
+ * the smallest doc id admitted, inclusive -- no doc id has a special meaning.  A value out of range fails the call
+ * with NXS_ERR_INVALID and a message that names the key.  nxs_index_match_docs_batch: from == NULL, or from[i]
+ * replaces "match_from" for query i.
+ *
+ * RESULT.  The docs of M with id >= from, in ascending doc id, the first "match_limit" of them: nxs_docs_count of
+ * them at nxs_docs_ids (owned by the object).  nxs_docs_total = |M|, whatever the cursor.  nxs_docs_next is true
+ * exactly when a doc of M lies beyond the page; *from is then the last returned id + 1 (it cannot overflow: a larger
+ * id exists), the cursor of the next page; false = the set is exhausted (*from is left alone).  Pages walked from
+ * 0 until nxs_docs_next is false are disjoint, ascending, and their concatenation is M of a snapshot that does not
+ * change meanwhile; after a refresh the walk goes on from its cursor over the new M.  The ids are ascending and
+ * distinct, which is the one-pass fast path of nxs_index_search_docs: match_docs(q1) then search_docs(q2, ids) is
+ * an exact search within the results of q1.  nxs_docs_tojson:
+ *   {"query":"<the string as given>","docs":[1,5,9],"count":3,"total":120,"next":10}
+ * "next" is absent when the set is exhausted; strings with the escaping rules of nxs_sugg_tojson.  The text is
+ * malloc()ed: free() it.
+ *
+ * EDGE CASES.  A query that resolves to nothing, or an empty M: an empty page with total 0, not an error.  A
+ * parse error is what a search reports for the string.  More than 32 live tokens (a search's wide plan):
+ * NXS_ERR_LIMIT "match_docs is not available for a query of more than 32 terms".  In a batch both are errs[i], and
+ * the batch goes on.  nxs_index_match_docs_batch returns the number of failed queries, or -1 if the batch as a
+ * whole could not run.
+ *
+ * Everything else is nxs_index_related's: the call re-syncs with the files, is allowed with batches or a pending
+ * fuzzy pass in flight and neither reorders them nor changes their responses, is blocking on a stream and
+ * workspace of its own, is local under a communicator, and on a handle from nxs_index_open_shard fails with
+ * NXS_ERR_INVALID "match_docs is not available on a doc shard" (the shards' pages would concatenate: a follow-up).
+ */
+#define	NXS_MATCH_MAX		(1u << 22)
+struct nxs_docs;
+typedef struct nxs_docs nxs_docs_t;
+
+nxs_docs_t *	nxs_index_match_docs(nxs_index_t *, nxs_params_t *, const char *query, size_t len);
+int		nxs_index_match_docs_batch(nxs_index_t *, nxs_params_t *, const char *const *queries, size_t n,
+		    const nxs_doc_id_t *from /* NULL, or [n]: per-query cursors */, nxs_docs_t **out, nxs_err_t *errs);
+size_t		nxs_docs_count(const nxs_docs_t *);
+const nxs_doc_id_t *nxs_docs_ids(const nxs_docs_t *);		/* [count], ascending; owned by the object */
+uint64_t	nxs_docs_total(const nxs_docs_t *);		/* |M|, whatever the cursor */
+bool		nxs_docs_next(const nxs_docs_t *, nxs_doc_id_t *from);	/* true + cursor of the next page, false = exhausted */
+char *		nxs_docs_tojson(nxs_docs_t *, size_t *);
+void		nxs_docs_release(nxs_docs_t *);
 
 /*
  * Batch entry point (new).  Runs `n` queries with one set of params as one

@@ -538,6 +538,44 @@ int		nxsgpu_search_docs(nxsgpu_index_t *, int algo, uint64_t limit, const nxsgpu
 void		nxsgpu_search_docs_profile(nxsgpu_index_t *, double out[NXSGPU_DOCSET_PROF], int reset);
 
 /*
+ * ---- a query's matches listed by doc id ---------------------------------------------------
+ *
+ * nxsgpu_match_docs: for each of n plans the doc set M of the plan's expression -- exactly what nxsgpu_count counts
+ * and what nxsgpu_related calls M: live docs, empty under a ranking function that scores nothing -- as a PAGE: the
+ * docs of M whose id is >= from[i], in ascending doc id, the first `limit` (1..NXSGPU_MATCH_MAX) of them.  ids is
+ * [n][cap] with cap = min(limit, nxsgpu_index_docs()); row i holds counts[i] ids, more[i] = a doc of M lies beyond
+ * the page, totals[i] = |M| whatever the cursor.  A plan that is empty or matches nothing has counts 0 and totals
+ * 0.  (plan, from) pairs that are identical are answered once and copied.  No impact is read: nothing is
+ * materialised.  A plan of more than 8 tokens is evaluated from its postfix program: a program that nxs_ds_prog_ok
+ * (csrc/nxs_docset.h) refuses fails the call.  0 / -1.
+ *
+ * Doc ordinals ascend with doc ids, so a page is a stream compaction of M's bits.  A pass serves a group of G <= 32
+ * distinct pairs: k_md_mask writes the doc sets as bits (a u32 per doc ordinal; k_count_tile's body, as k_rt_mask),
+ * k_md_from turns the cursors into ordinals (a lower bound over the doc ids, csrc/nxs_matchdocs.h), k_md_count --
+ * a wavefront per run of NXS_GPU_MATCHDOCS_RUN (default 256; a multiple of 64, 64..65536) ordinals -- counts every
+ * pair's docs at or beyond its cursor per run by ballot, one plain store per (pair, run), k_md_scan turns a pair's
+ * row into ranks (one workgroup per pair), k_md_emit walks the runs again and stores the doc id of every match
+ * whose rank is below the limit at ids[g][rank]: ascending and deterministic by construction.  Per pass: 4 B a doc
+ * for the masks, 4 B per (pair, run), 8 B x cap per pair, within NXS_GPU_MATCHDOCS_WS (default
+ * NXSGPU_MATCHDOCS_WS) bytes: G is what fits, one pair at least, and a batch is cut into passes of G pairs.  The
+ * pass has a stream, a grow-only workspace, pinned staging and events of its own: allowed while batches and fuzzy
+ * passes are in flight, takes none of their slots; blocking.  An index that is never asked allocates, uploads and
+ * launches nothing.  Under NXS_GPU_MATCHDOCS=host (the cross-check route) the posting array and the doc ids are
+ * copied back, the doc set is evaluated from the plan's postfix program on the host and the page is nxs_md_page's.
+ *
+ * nxsgpu_match_docs_profile: since the last reset -- out[0] distinct pairs answered on the device, out[1] on the
+ * host, out[2] passes, out[3] ids emitted, out[4] .. out[8] HIP-event ms of k_md_mask / k_md_from / k_md_count /
+ * k_md_scan / k_md_emit (with nxsgpu_set_profiling only), out[9] calls that had a pair to answer.
+ */
+#define	NXSGPU_MATCH_MAX	(1u << 22)
+#define	NXSGPU_MATCHDOCS_PROF	10
+#define	NXSGPU_MATCHDOCS_WS	(256ull << 20)
+int		nxsgpu_match_docs(nxsgpu_index_t *, int algo, const nxsgpu_query_t *plans, uint32_t n,
+		    const uint64_t *from /* [n] */, uint32_t limit, uint64_t *ids /* [n][cap] */,
+		    uint32_t *counts, uint8_t *more, uint32_t *totals);		/* [n] */
+void		nxsgpu_match_docs_profile(nxsgpu_index_t *, double out[NXSGPU_MATCHDOCS_PROF], int reset);
+
+/*
  * ---- host batches as fixed-size records; query sharding over several GPUs ----
  *
  * The reference scales out by running independent worker processes

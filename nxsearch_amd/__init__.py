@@ -98,6 +98,8 @@ NXS_H_SYMBOLS = [
     "nxs_index_similar", "nxs_index_similar_batch",
     "nxs_index_related", "nxs_index_related_batch", "nxs_sugg_docs",
     "nxs_index_search_docs", "nxs_index_search_docs_batch",
+    "nxs_index_match_docs", "nxs_index_match_docs_batch", "nxs_docs_count", "nxs_docs_ids", "nxs_docs_total",
+    "nxs_docs_next", "nxs_docs_tojson", "nxs_docs_release",
 ]
 # csrc/nxs_hooks.h: test hooks + bench accessors, only in builds with -DNXS_TEST_HOOKS (the default)
 NXS_HOOK_SYMBOLS = ["nxs_index_device", "nxs_index_host_profile", "nxs_index_shard_info", "nxs_test_pool", "nxs_test_assemble",
@@ -115,7 +117,8 @@ NXS_HOOK_SYMBOLS = ["nxs_index_device", "nxs_index_host_profile", "nxs_index_sha
                     "nxs_test_docterms_key", "nxs_test_similar_drop",
                     "nxs_test_related_params", "nxs_test_related_build", "nxs_test_related_key",
                     "nxs_test_related_share", "nxs_test_related_eligible", "nxs_test_related_rank",
-                    "nxs_test_docset_sort", "nxs_test_docset_lane"]
+                    "nxs_test_docset_sort", "nxs_test_docset_lane",
+                    "nxs_test_match_params", "nxs_test_docs_build", "nxs_test_md_lower_bound", "nxs_test_md_page"]
 NXS_GPU_H_SYMBOLS = [
     "nxsgpu_device_count", "nxsgpu_last_error", "nxsgpu_index_create",
     "nxsgpu_index_destroy", "nxsgpu_index_df", "nxsgpu_index_postings",
@@ -140,6 +143,7 @@ NXS_GPU_H_SYMBOLS = [
     "nxsgpu_doc_terms", "nxsgpu_doc_terms_profile",
     "nxsgpu_related", "nxsgpu_related_profile",
     "nxsgpu_search_docs", "nxsgpu_search_docs_profile",
+    "nxsgpu_match_docs", "nxsgpu_match_docs_profile",
 ]
 
 # nxs_test_index_image (csrc/nxs_hooks.h): part numbers and the order of the scalars, as nxsgpu_test_index_image
@@ -389,6 +393,37 @@ def lib():
                                      C.c_uint32, u32p, C.POINTER(GpuResults), u32p]
     L.nxsgpu_search_docs_profile.restype = None
     L.nxsgpu_search_docs_profile.argtypes = [vp, C.POINTER(C.c_double), C.c_int]
+    L.nxs_index_match_docs.restype = vp
+    L.nxs_index_match_docs.argtypes = [vp, vp, C.c_char_p, C.c_size_t]
+    L.nxs_index_match_docs_batch.restype = C.c_int
+    L.nxs_index_match_docs_batch.argtypes = [vp, vp, C.POINTER(C.c_char_p), C.c_size_t, u64p, C.POINTER(vp),
+                                             C.POINTER(C.c_int)]
+    L.nxs_docs_count.restype = C.c_size_t
+    L.nxs_docs_count.argtypes = [vp]
+    L.nxs_docs_ids.restype = u64p
+    L.nxs_docs_ids.argtypes = [vp]
+    L.nxs_docs_total.restype = C.c_uint64
+    L.nxs_docs_total.argtypes = [vp]
+    L.nxs_docs_next.restype = C.c_bool
+    L.nxs_docs_next.argtypes = [vp, u64p]
+    L.nxs_docs_tojson.restype = vp
+    L.nxs_docs_tojson.argtypes = [vp, C.POINTER(C.c_size_t)]
+    L.nxs_docs_release.restype = None
+    L.nxs_docs_release.argtypes = [vp]
+    L.nxsgpu_match_docs.restype = C.c_int
+    L.nxsgpu_match_docs.argtypes = [vp, C.c_int, C.POINTER(GpuQuery), C.c_uint32, u64p, C.c_uint32, u64p, u32p,
+                                    C.POINTER(C.c_uint8), u32p]
+    L.nxsgpu_match_docs_profile.restype = None
+    L.nxsgpu_match_docs_profile.argtypes = [vp, C.POINTER(C.c_double), C.c_int]
+    if hasattr(L, "nxs_test_match_params"):
+        L.nxs_test_match_params.restype = C.c_int
+        L.nxs_test_match_params.argtypes = [vp, vp, C.POINTER(C.c_uint), u64p]
+        L.nxs_test_docs_build.restype = vp
+        L.nxs_test_docs_build.argtypes = [C.c_char_p, u64p, C.c_size_t, C.c_uint64, C.c_bool]
+        L.nxs_test_md_lower_bound.restype = C.c_uint64
+        L.nxs_test_md_lower_bound.argtypes = [u64p, C.c_uint64, C.c_uint64]
+        L.nxs_test_md_page.restype = C.c_uint64
+        L.nxs_test_md_page.argtypes = [u32p, u64p, C.c_uint64, C.c_uint64, C.c_uint64, u64p, C.POINTER(C.c_bool)]
     if hasattr(L, "nxs_test_docset_sort"):
         L.nxs_test_docset_sort.restype = C.c_size_t
         L.nxs_test_docset_sort.argtypes = [u64p, C.c_size_t]
@@ -740,6 +775,34 @@ def _drain_related(sg, json=False):
         return out
     finally:
         L.nxs_sugg_release(sg)
+
+
+class Docs(list):
+    """A page of a query's matches (nxs_docs_t of nxs_index_match_docs): doc ids, ascending, with `.total` = the
+    size of the query's doc set whatever the cursor and `.next` = the cursor of the next page (None: the set is
+    exhausted)."""
+    total = 0
+    next = None
+
+
+def _drain_docs(d, json=False):
+    """nxs_docs_t -> Docs (or its JSON text); releases the object"""
+    L = lib()
+    try:
+        if json:
+            n = C.c_size_t()
+            return _take(L.nxs_docs_tojson(d, C.byref(n)))
+        out = Docs()
+        n = L.nxs_docs_count(d)
+        if n:
+            import numpy as np
+            out.extend(np.ctypeslib.as_array(L.nxs_docs_ids(d), shape=(n,)).tolist())
+        out.total = L.nxs_docs_total(d)
+        nxt = C.c_uint64()
+        out.next = nxt.value if L.nxs_docs_next(d, C.byref(nxt)) else None
+        return out
+    finally:
+        L.nxs_docs_release(d)
 
 
 def _drain_sugg(sg, json=False):
@@ -1371,6 +1434,49 @@ class Index:
             else:
                 out.append(NxsError(errs[i], "query %d failed" % i))
         return out
+
+    def match_docs(self, queries, limit=None, start=None, algo=None, fuzzymatch=None, prefixmatch=None,
+                   wildcardmatch=None, json=False):
+        """nxs_index_match_docs_batch(): for every query string the docs its expression matches -- the set "total"
+        counts -- with id >= `start` (one id for all queries, or one per query; default 0) in ascending doc id, the
+        first `limit` (1..2^22, default 1000) of them -> a list of Docs, one per query: a list of ints with
+        `.total` = the size of the whole set and `.next` = the cursor of the next page, None when the set is
+        exhausted (an NxsError instance in the slot of a query that failed: a parse error, more than 32 terms);
+        json: their JSON texts."""
+        L = lib()
+        n = len(queries)
+        p = _make_params(None, algo, fuzzymatch, False, prefixmatch, None, False, wildcardmatch, None)
+        frm = None
+        if start is not None and hasattr(start, "__len__"):
+            if len(start) != n:
+                raise ValueError("match_docs: one start for all queries, or one per query")
+            frm = (C.c_uint64 * max(n, 1))(*start)
+        if limit is not None or (start is not None and frm is None):
+            p = p or L.nxs_params_create()
+            if limit is not None:
+                L.nxs_params_set_uint(p, b"match_limit", limit)
+            if start is not None and frm is None:
+                L.nxs_params_set_uint(p, b"match_from", start)
+        out = (C.c_void_p * max(n, 1))()
+        errs = (C.c_int * max(n, 1))()
+        qs = (C.c_char_p * max(n, 1))(*[_b(q) for q in queries])
+        try:
+            r = L.nxs_index_match_docs_batch(self._h, p, qs, n, frm, out, errs)
+        finally:
+            if p:
+                L.nxs_params_release(p)
+        if r < 0:
+            self.nxs._raise()
+        return [_drain_docs(out[i], json) if out[i] else NxsError(errs[i], "query %d failed" % i) for i in range(n)]
+
+    def match_docs_profile(self, reset=False):
+        """nxsgpu_match_docs_profile(): distinct (plan, cursor) pairs answered on the device / on the host, passes,
+        ids emitted, HIP-event ms per kernel (profiling on), calls that had a pair to answer."""
+        out = (C.c_double * 10)()
+        lib().nxsgpu_match_docs_profile(self.device, out, 1 if reset else 0)
+        return {"device_pairs": int(out[0]), "host_pairs": int(out[1]), "passes": int(out[2]), "ids": int(out[3]),
+                "mask_ms": out[4], "from_ms": out[5], "count_ms": out[6], "scan_ms": out[7], "emit_ms": out[8],
+                "calls": int(out[9])}
 
     def search_docs_profile(self, reset=False):
         """nxsgpu_search_docs_profile(): calls that reached the device, passes, distinct sets and ids resolved,

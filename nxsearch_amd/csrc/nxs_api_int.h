@@ -9,6 +9,7 @@
  *   nxs_batch.c     begin / end, the late second half, exact fix-up and its protocol, query sharding
  *   nxs_lookup.c    nxs_sugg_t, suggest, complete, wildcard, doc_terms, related
  *   nxs_searchdocs.c  search within a caller's doc-id set (search_docs)
+ *   nxs_matchdocs.c   a query's matches listed by doc id (match_docs), nxs_docs_t
  *   nxs_docshard.c  doc-sharded collections: search, attach, refresh
  *   nxs_hooks.c     the test hooks that reach no static
  *
@@ -78,6 +79,14 @@ typedef struct {
 } related_params_t;
 
 int	get_related_params(nxs_t *, const nxs_params_t *, related_params_t *);
+
+/* nxs_index_match_docs' own keys (the query is read with a search's: search_params_t) */
+typedef struct {
+	unsigned	limit;		/* "match_limit": ids per page (1..NXS_MATCH_MAX, default 1000) */
+	uint64_t	from;		/* "match_from": the smallest doc id admitted (default 0) */
+} match_params_t;
+
+int	get_match_params(nxs_t *, const nxs_params_t *, match_params_t *);
 
 /* ---- nxs_resp.c ----------------------------------------------------------------------- */
 

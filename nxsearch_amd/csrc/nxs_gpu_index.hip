@@ -155,6 +155,12 @@ cfg_from_env(gpu_cfg_t &c)
 	}
 	c.docset_chunk = std::max<uint32_t>(WAVE, (uint32_t)u64("NXS_GPU_DOCSET_CHUNK", 1024, 64, 1u << 16) / WAVE * WAVE);
 	c.docset_ws = u64("NXS_GPU_DOCSET_WS", NXSGPU_DOCSET_WS, 1, 1ull << 34);
+	{
+		const char *e = getenv("NXS_GPU_MATCHDOCS");
+		c.matchdocs_host = e && !strcmp(e, "host");
+	}
+	c.matchdocs_run = std::max<uint32_t>(WAVE, (uint32_t)u64("NXS_GPU_MATCHDOCS_RUN", 256, 64, 1u << 16) / WAVE * WAVE);
+	c.matchdocs_ws = u64("NXS_GPU_MATCHDOCS_WS", NXSGPU_MATCHDOCS_WS, 1, 1ull << 34);
 }
 
 /* ------------------------------------------------------------------ */
@@ -688,6 +694,7 @@ nxsgpu_index_destroy(nxsgpu_index_t *ix)
 	dv_free(ix);
 	rt_free(ix);
 	ds_free(ix);
+	md_free(ix);
 	bk_aux_free(ix);
 	(void)hipFree(ix->ws);
 	(void)hipFree(ix->fz);

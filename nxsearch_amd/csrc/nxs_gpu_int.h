@@ -42,7 +42,10 @@
  *  nxs_gpu_docset.hip     a search within a caller's doc-id set: the sets' ordinals (k_ds_ord), every (query, doc of its set)
  *                         scored by lookups from the doc's side (k_ds_score; nxs_docset.h) into candidate segments, then
  *                         k_replay
- *  nxs_gpu_side.hip       host only: what the seven blocking side passes above share -- stream, workspace, staging and
+ *  nxs_gpu_matchdocs.hip  a query's matches by doc id: the doc sets of a group of (plan, cursor) pairs as bits (k_md_mask:
+ *                         k_count_tile's body), the cursors as ordinals (k_md_from), then a stream compaction of the bits --
+ *                         count per run (k_md_count), scan (k_md_scan), emit (k_md_emit); nxs_matchdocs.h
+ *  nxs_gpu_side.hip       host only: what the eight blocking side passes above share -- stream, workspace, staging and
  *                         events (side_t), the host rankers' dictionary, the term-list download block
  *  nxs_gpu_plan.hip       host only: query classes, the work list (build_worklist) and
  *                         the layout of a batch's arrays (batch_layout)
@@ -218,6 +221,12 @@ struct gpu_cfg_t {
 					 * candidate segment; a multiple of 64, 64 at least */
 	uint64_t	docset_ws;	/* NXS_GPU_DOCSET_WS (256 MiB): bytes of workspace per pass; a larger batch is cut into passes
 					 * of whole queries (one at least) */
+	bool		matchdocs_host;	/* NXS_GPU_MATCHDOCS=host: doc sets from nxs_ds_eval and pages from nxs_md_page (nxs_matchdocs.h)
+					 * on the host over copies of d_post_dt and d_doc_ids: the cross-check */
+	uint32_t	matchdocs_run;	/* NXS_GPU_MATCHDOCS_RUN (256): doc ordinals per wavefront of k_md_count / k_md_emit; a multiple
+					 * of 64, 64..65536 */
+	uint64_t	matchdocs_ws;	/* NXS_GPU_MATCHDOCS_WS (256 MiB): bytes of masks, run counts and pages per pass; the group is
+					 * what fits (one pair at least, 32 at most), a larger batch is cut into passes */
 };
 enum : uint32_t { COUNT_AUTO = 0, COUNT_TILE = 1, COUNT_REQ = 2, COUNT_SCAN = 3 };
 
@@ -448,6 +457,8 @@ struct nxsgpu_index {
 	struct rt_state_t *rt;
 	/* search within a doc-id set (nxsgpu_search_docs, nxs_gpu_docset.hip): the same; nothing until the first call */
 	struct ds_state_t *ds;
+	/* a query's matches by doc id (nxsgpu_match_docs, nxs_gpu_matchdocs.hip): the same; nothing until the first call */
+	struct md_state_t *md;
 };
 
 static inline uint32_t __device__ __host__
@@ -681,7 +692,7 @@ void	sg_free(nxsgpu_index_t *ix);		/* everything nxsgpu_suggest has built (index
 
 /* ---- nxs_gpu_side.hip ---- */
 /*
- * What every blocking side pass (suggest, complete, wildcard, explain, doc terms, related, search_docs) owns beside its own
+ * What every blocking side pass (suggest, complete, wildcard, explain, doc terms, related, search_docs, match_docs) owns beside its own
  * data: a non-blocking stream, a grow-only device workspace, grow-only pinned staging and, once profiling is on,
  * its events.  Zero-initialised with the pass's state; nothing exists until side_open / side_room make it.
  */
@@ -792,6 +803,9 @@ void	rt_free(nxsgpu_index_t *ix);		/* everything nxsgpu_related has built (index
 
 /* ---- nxs_gpu_docset.hip ---- */
 void	ds_free(nxsgpu_index_t *ix);		/* everything nxsgpu_search_docs has built (index destroy) */
+
+/* ---- nxs_gpu_matchdocs.hip ---- */
+void	md_free(nxsgpu_index_t *ix);		/* everything nxsgpu_match_docs has built (index destroy) */
 
 /* ---- nxs_gpu_plan.hip ---- */
 void	delete_worklist(worklist_t *);

@@ -17,6 +17,7 @@
 #include "nxs_docterms.h"
 #include "nxs_related.h"
 #include "nxs_docset.h"
+#include "nxs_matchdocs.h"
 
 char *
 nxs_test_query_repr(const char *query, char **errmsg)
@@ -297,6 +298,20 @@ nxs_test_related_rank(int order, const uint32_t *c, const uint32_t *df, uint32_t
     uint32_t mindf, const uint32_t *excl, uint32_t n_excl, uint32_t k, uint32_t *out_ids, uint64_t *matches)
 {
 	return nxs_rt_rank(order, c, df, n_terms, mincount, mindf, excl, n_excl, k, out_ids, matches);
+}
+
+/* nxs_matchdocs.h over caller arrays */
+uint64_t
+nxs_test_md_lower_bound(const uint64_t *ids, uint64_t n, uint64_t from)
+{
+	return nxs_md_lower_bound(ids, n, from);
+}
+
+uint64_t
+nxs_test_md_page(const uint32_t *in_bits, const uint64_t *doc_ids, uint64_t D, uint64_t from, uint64_t limit,
+    uint64_t *out, bool *more)
+{
+	return nxs_md_page(in_bits, doc_ids, D, from, limit, out, more);
 }
 
 /* nxs_docset.h: the set as the device wants it, and one lane of k_ds_score over arrays handed in */

@@ -196,5 +196,15 @@ int		nxs_test_docset_lane(const uint64_t *dt, const float *imp, const uint64_t *
 		    uint32_t n_docs, const uint32_t *truth, const uint8_t *prog, uint32_t prog_len, const uint32_t *ords,
 		    size_t nd, uint8_t *hit, float *score);
 
+/* a query's matches by doc id: nxs_index_match_docs' own parameters as it reads them (0, or -1 with the error
+ * declared), an nxs_docs_t built by hand, and nxs_matchdocs.h over caller arrays: the lower bound of `from` in
+ * ids[0 .. n), and a page of the set in_bits ((D + 31) / 32 words, a bit per doc ordinal) -> ids written to out
+ * (room for min(limit, D)), *more = a doc of the set lies beyond them */
+int		nxs_test_match_params(nxs_t *, nxs_params_t *, unsigned *limit, uint64_t *from);
+nxs_docs_t *	nxs_test_docs_build(const char *query, const uint64_t *ids, size_t count, uint64_t total, bool more);
+uint64_t	nxs_test_md_lower_bound(const uint64_t *ids, uint64_t n, uint64_t from);
+uint64_t	nxs_test_md_page(const uint32_t *in_bits, const uint64_t *doc_ids, uint64_t D, uint64_t from,
+		    uint64_t limit, uint64_t *out, bool *more);
+
 #endif /* NXS_TEST_HOOKS */
 #endif /* NXS_HOOKS_H */

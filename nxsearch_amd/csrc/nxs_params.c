@@ -687,3 +687,31 @@ get_related_params(nxs_t *nxs, const nxs_params_t *params, related_params_t *rp)
 	}
 	return 0;
 }
+
+/*
+ * The parameters of nxs_index_match_docs, validated as the related_* keys are: "match_limit" (uint,
+ * 1..NXS_MATCH_MAX, default 1000) and "match_from" (uint, default 0: any doc id is a cursor).  0, or -1 with
+ * NXS_ERR_INVALID and a message that names the key.
+ */
+int
+get_match_params(nxs_t *nxs, const nxs_params_t *params, match_params_t *mp)
+{
+	uint64_t v;
+
+	mp->limit = 1000;
+	mp->from = 0;
+	if (!params) {
+		return 0;
+	}
+	if (nxs_params_get_uint(params, "match_limit", &v) == 0) {
+		if (v < 1 || v > NXS_MATCH_MAX) {
+			nxs_decl_err(nxs, NXS_ERR_INVALID, "invalid match_limit (1..%u)", NXS_MATCH_MAX);
+			return -1;
+		}
+		mp->limit = (unsigned)v;
+	}
+	if (nxs_params_get_uint(params, "match_from", &v) == 0) {
+		mp->from = v;
+	}
+	return 0;
+}
